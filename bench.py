@@ -2,7 +2,16 @@
 """Headline benchmark: coordinate-samples/sec of one full training step (on-device batch
 generation -> forward -> MSE -> backward -> [RCCL all-reduce] -> Adam) on a synthetic volume.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload cfg4|cfg2|cfg3]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload cfg4|cfg2|cfg3] [--full]
+                    [--dump-outputs DIR]
+
+A plain run does what the headline figure needs: set-up, the untimed training steps that settle the
+device (--psnr-steps of them), W warm-up steps, K timed steps, the result line.  --full adds what is
+measured beside it: the PSNR of the trained network, a timed leg with the other table-gradient record
+format and the CPU baseline.  --dump-outputs DIR writes what the timed path returned in its last timed
+step as DIR/<name>.npy (float32): `loss`, and `param.<name>` for every parameter after that step's
+Adam update (predict mode: `pred`, the last batch's predictions); a parameter of more than 2^21 values
+is written as the fixed sample of 2^21 of them that seed DUMP_SEED draws (sorted flat indices).
 
 N > 1 is launched by the driver as `python -m torch.distributed.run --nproc-per-node N ...`:
 one rank per GPU, z-slab sharding of the volume, equal local batch (weak scaling), ONE
@@ -54,6 +63,31 @@ RECORDS = {
 
 def arithmetic(records):
     return ARITHMETIC + RECORDS[records][1]
+
+
+DUMP_SAMPLE = 1 << 21  # values kept of a larger parameter: the dump stays well below 64 MB
+DUMP_SEED = 20261016
+
+
+def step_outputs(model, loss):
+    """What a caller of the training step holds after it: the loss and the updated parameters (host copies)."""
+    import numpy as np
+    out = {"loss": np.array([loss], dtype=np.float32)}
+    for name, p in model.named_parameters():
+        a = p.detach().float().cpu().numpy().ravel()
+        if a.size > DUMP_SAMPLE:
+            a = a[np.sort(np.random.default_rng(DUMP_SEED).choice(a.size, DUMP_SAMPLE, replace=False))]
+        out["param." + name] = a
+    return out
+
+
+def dump_outputs(directory, arrays):
+    import numpy as np
+    assert sum(a.nbytes for a in arrays.values()) <= 64 << 20, "outputs dump over 64 MB"
+    os.makedirs(directory, exist_ok=True)
+    for name, a in arrays.items():
+        assert a.dtype in (np.float32, np.float64), (name, a.dtype)
+        np.save(os.path.join(directory, name + ".npy"), a)
 
 
 def mfma_roof(step, achieved_tf):
@@ -237,6 +271,8 @@ def run_predict(args, w, vol, step, model, rank, world, dev, data_name):
         torch.distributed.destroy_process_group()
     if rank != 0:
         return
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"pred": pred.detach().float().cpu().numpy()})
     dims = [l.weight.shape[1] for l in step.layers] + [step.layers[-1].weight.shape[0]]
     mac = sum(dims[i] * dims[i + 1] for i in range(len(dims) - 1))
     pm = {"mlp_fwd": ("mfma", 2.0 * mac * batch)}
@@ -282,8 +318,15 @@ def main():
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=50)
     ap.add_argument("--workload", default="cfg4", choices=sorted(WORKLOADS))
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what is reported beside the headline: the PSNR evaluation, the timed leg "
+                         "with the other record format and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the loss and parameters of the last timed step (predict: its predictions) as "
+                         "DIR/<name>.npy")
     ap.add_argument("--psnr-steps", type=int, default=None,
-                    help="total training steps before the PSNR evaluation (0 = skip; default 2000, "
+                    help="total training steps before the PSNR evaluation; one GPU: they run untimed before the "
+                         "timed legs, to settle the device, also without --full (0 = skip; default 2000, "
                          "SIREN workloads 200)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--batch-group", type=int, default=1,
@@ -628,12 +671,13 @@ def main():
         return max(ok, key=lambda k: legs[k]["value"])
 
     def quality_train():
-        """Train on to the fixed step count the PSNR is quoted at; returns (steps, a copy of the parameters there)."""
+        """Train on to the fixed step count the PSNR is quoted at; returns (steps, a copy of the parameters there
+        when the PSNR is evaluated: --full)."""
         while counter[0] < args.psnr_steps:
             one_step()
         if graphed[0] is not None:
             graphed[0].finish()
-        return counter[0], [p.detach().clone() for p in model.parameters()]
+        return counter[0], [p.detach().clone() for p in model.parameters()] if args.full else None
 
     def quality_eval(steps, snapshot):
         """PSNR vs ground-truth voxels of the parameters saved at `steps` (outside the timed region)."""
@@ -680,7 +724,9 @@ def main():
     capture_graphs()
     if warm_first:
         quality = quality_train()
-        device_warmup = f"the quality leg's {quality[0]} training steps of this workload ran before the timed legs"
+        device_warmup = (f"the quality leg's {quality[0]} training steps of this workload ran before the timed legs"
+                         if args.full else f"{quality[0]} untimed training steps of this workload ran before the "
+                                           "timed legs (the quality leg's; its PSNR is evaluated with --full)")
     elif not args.cold_start and world > 1:
         n_warm = min(4000, max(1, int(1.0 / max(1e-4, timed_leg(2, 8)["ms_per_step"] * 1e-3))))
         timed_leg(0, n_warm)
@@ -709,6 +755,8 @@ def main():
                    groups=[dict(bytes=b, wait_ms=round(leg["phases"].get(f"reduce_wait_{j}", 0.0), 4))
                            for j, b in enumerate(getattr(step, "last_group_bytes", []))]
                    if world > 1 else [])
+        if args.dump_outputs and rank == 0:
+            leg["outputs"] = step_outputs(model, leg["loss"])
         legs[name] = leg
         if rank == 0 and world > 1:
             partial_line[0] = finish(best_leg()) if any(v["identical"] for v in legs.values()) else None
@@ -719,13 +767,13 @@ def main():
             graphed[0].finish()
         capture_graphs()
 
-    if not warm_first and args.psnr_steps > 0:
+    if args.full and not warm_first and args.psnr_steps > 0:
         quality = quality_train()
         psnr = quality_eval(*quality)
     # the other record format beside the headline (one GPU, grids with two features per level): the same
     # model and loader, the same number of timed steps
     packed = None
-    if (world == 1 and step.encoder is not None and step.encoder.n_features_per_level == 2
+    if (args.full and world == 1 and step.encoder is not None and step.encoder.n_features_per_level == 2
             and not args.no_records_leg and args.bwd_method != 1):
         other = "packed" if args.records == "f32" else "f32"
         _lib.set_option("bwd_records", RECORDS[other][0])
@@ -736,7 +784,7 @@ def main():
         packed = dict(records=other, value=leg["value"], ms_per_step=leg["ms_per_step"],
                       phases_ms={k: round(v, 4) for k, v in sorted(leg["phases"].items())},
                       arithmetic=RECORDS[other][1])
-    if warm_first:
+    if warm_first and args.full:
         psnr = quality_eval(*quality)
     if world > 1:  # leave the process group together (rank 0 was busy with the PSNR pass)
         import torch.distributed as dist
@@ -744,7 +792,9 @@ def main():
         dist.destroy_process_group()
     if rank != 0:
         return
-    cpu = cpu_baseline(w, args.workload) if world == 1 and not args.no_cpu_baseline else None
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, legs[best]["outputs"])
+    cpu = cpu_baseline(w, args.workload) if args.full and world == 1 and not args.no_cpu_baseline else None
     print(json.dumps(finish(best, psnr, packed, cpu)), flush=True)
 
 

@@ -360,6 +360,62 @@ def round3_fixtures(encoding, models):
               dims=[4, 64, 1], lr=5e-3, steps=2, batch=320), **arrays)
 
 
+def standalone_fixtures(encoding, models):
+    """Fixtures that let two tests run without the reference present (the earlier ones stay byte-identical):
+    `reference_checkpoint` -- what a strict `load_state_dict` and `opt.load_state_dict` of the reference's
+    HashMLP / SirenNet check (state-dict keys and shapes, parameter order, the Adam `configure_optimizers`
+    builds, models.py:68-70) and the reference SirenNet's forward on a checkpoint of this package;
+    `sample_nifti_header` -- the header bytes of the sample NIfTI, which with sample_volume.npz's voxels
+    rebuild the decompressed file byte for byte (its SHA-256 is kept to prove it)."""
+    import hashlib
+    from mri_interpolation_amd import checkpoint, models as amd_models
+    ctors = {  # tests/test_checkpoint_cpu.py's _hash() / _siren() and their reference counterparts
+        "hash": (dict(dim_in=3, dim_hidden=16, dim_out=1, n_layers=2, n_levels=3, n_features_per_level=2,
+                      log2_hashmap_size=9, base_resolution=4, finest_resolution=32, lr=5e-3), models.HashMLP),
+        "siren": (dict(dim_in=3, dim_hidden=16, dim_out=1, n_layers=3, lr=1e-4), models.SirenNet),
+    }
+    meta, arrays = {}, {}
+    for kind, (kw, cls) in ctors.items():
+        ref = cls(**kw)
+        opt = ref.configure_optimizers()
+        names = [n for n, _ in ref.named_parameters()]
+        entry = dict(ctor=kw, state=[[k, list(v.shape)] for k, v in ref.state_dict().items()], param_names=names,
+                     optimizer=dict(cls=type(opt).__name__, **{k: (list(v) if isinstance(v, tuple) else v)
+                                                               for k, v in opt.defaults.items()
+                                                               if k in ("lr", "betas", "eps", "weight_decay",
+                                                                        "amsgrad")}))
+        if kind == "siren":
+            # this package's SirenNet with seeded parameters -> its checkpoint state dict -> the reference's forward
+            own = amd_models.SirenNet(**kw)
+            with torch.no_grad():
+                for i, p in enumerate(own.parameters()):
+                    p.copy_(torch.from_numpy(detrand.uniform(p.numel(), 1300 + i, -0.5, 0.5).reshape(p.shape)))
+            sd = checkpoint.reference_state_dict(own)
+            result = ref.load_state_dict(sd, strict=True)
+            assert not result.missing_keys and not result.unexpected_keys
+            by_id = {id(p): n for n, p in ref.named_parameters()}
+            entry["forward_layers"] = [[by_id[id(l.weight)], by_id[id(l.bias)]]
+                                       for l in list(ref.layers) + [ref.last_layer]]
+            x = detrand.uniform(7 * 3, 1320, 0.0, 1.0).reshape(7, 3)
+            with torch.no_grad():
+                arrays["siren_y"] = ref(torch.from_numpy(x)).numpy().copy()
+            arrays["siren_x"] = x
+            for i, k in enumerate(sd):
+                arrays[f"siren_sd_{i}"] = sd[k].numpy().copy()
+            entry["param_seeds"] = [1300, "+ parameter index"]
+        meta[kind] = entry
+    save("reference_checkpoint", meta, **arrays)
+
+    raw = gzip.open(os.path.join(REF, "sample_ankle_dyn_mri.nii.gz")).read()
+    vox_offset = int(struct.unpack("<f", raw[108:112])[0])
+    vol, shape, _, _ = read_sample_volume()
+    assert raw[:vox_offset] + np.asarray(vol, dtype="<i2").tobytes(order="F") == raw
+    save("sample_nifti_header", dict(vox_offset=vox_offset, sha256=hashlib.sha256(raw).hexdigest(),
+                                     source="sample_ankle_dyn_mri.nii.gz, decompressed",
+                                     voxels="sample_volume.npz raw_int16, F order"),
+         header=np.frombuffer(raw[:vox_offset], dtype=np.uint8).copy())
+
+
 def main():
     torch.manual_seed(1337)
     torch.set_num_threads(4)
@@ -370,6 +426,8 @@ def main():
         return round3_fixtures(encoding, models)
     if "--round2-only" in sys.argv:
         return round2_fixtures(encoding, models)
+    if "--standalone-only" in sys.argv:
+        return standalone_fixtures(encoding, models)
 
     # ---- O1: hash ids (encoding.py:69-78) ------------------------------------------------
     arrays, cases = {}, []
@@ -566,6 +624,7 @@ def main():
     extra_models(encoding, models)
     round2_fixtures(encoding, models)
     round3_fixtures(encoding, models)
+    standalone_fixtures(encoding, models)
 
 
 if __name__ == "__main__":

@@ -132,7 +132,7 @@ def test_bench_one_rank_under_torchrun_is_the_plain_line(tmp_path):
         for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE") if not env_extra else ():
             env.pop(k, None)
         p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "40",
-                            "--warmup", "10", "--psnr-steps", "0", "--no-cpu-baseline"], env=env,
+                            "--warmup", "10", "--psnr-steps", "0", "--no-cpu-baseline", "--full"], env=env,
                            stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=420)
         assert p.returncode == 0, p.stdout
         out = [l for l in p.stdout.splitlines() if l.startswith("{")]
@@ -144,3 +144,39 @@ def test_bench_one_rank_under_torchrun_is_the_plain_line(tmp_path):
     assert plain["n_gpus"] == 1 and plain["config"]["parallelism"] == "single GPU" and "collectives" not in ranked
     assert plain["launch"].startswith("one mri_fused_step call") and "packed_records" in ranked
     assert abs(plain["value"] - ranked["value"]) <= 0.15 * plain["value"], (plain["value"], ranked["value"])
+
+
+def test_bench_plain_run_dumps_the_same_outputs_from_run_to_run(tmp_path):
+    """`bench.py --dump-outputs DIR` without --full: the headline line alone (no PSNR pass, no second record
+    format, no CPU baseline), exactly --steps timed steps, and the loss and parameters of the last timed step as
+    float32 .npy files under 64 MB -- the same bits in a second run with the same arguments."""
+    import numpy as np
+    import torch
+    if torch.cuda.is_initialized():
+        pytest.skip("the GPU is already initialised in this process: children may not be started")
+    dumps = []
+    for run in range(2):
+        out_dir = tmp_path / f"run{run}"
+        env = dict(os.environ)
+        for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE"):
+            env.pop(k, None)
+        p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "7",
+                            "--warmup", "3", "--workload", "cfg2", "--dump-outputs", str(out_dir)], env=env,
+                           stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=420)
+        assert p.returncode == 0, p.stdout
+        lines = [l for l in p.stdout.splitlines() if l.startswith("{")]
+        assert len(lines) == 1, p.stdout
+        r = json.loads(lines[0])
+        assert r["steps"] == 7 and r["warmup"] == 3 and r["ms_per_step"] > 0.0
+        assert abs(r["value"] - r["config"]["global_batch"] / (r["ms_per_step"] * 1e-3)) <= 1e-6 * r["value"]
+        assert not {"psnr", "packed_records", "cpu_baseline"} & set(r), sorted(r)
+        files = sorted(os.listdir(out_dir))
+        assert "loss.npy" in files and "param.encoder.table.npy" in files, files
+        arrays = {f: np.load(out_dir / f) for f in files}
+        assert all(a.dtype == np.float32 for a in arrays.values())
+        assert sum(a.nbytes for a in arrays.values()) <= 64 << 20
+        assert np.isfinite(arrays["loss.npy"]).all() and float(arrays["loss.npy"][0]) == r["final_loss"]
+        dumps.append(arrays)
+    assert sorted(dumps[0]) == sorted(dumps[1])
+    for f in dumps[0]:
+        assert np.array_equal(dumps[0][f], dumps[1][f]), f

@@ -1,19 +1,13 @@
 """Checkpoints in Lightning's layout (mri_interpolation_amd/checkpoint.py): what the reference's
 `model_cls.load_from_checkpoint` (reference launcher.py:97-117, strict) needs to be in the file, a round trip
-of parameters, Adam moments and step count, and -- where the reference is present (the build container) --
-a strict load into the reference's own classes and optimiser."""
-import os
-import sys
-
-import numpy as np
+of parameters, Adam moments and step count, and a strict load into the reference's own classes and optimiser
+(their keys, shapes, parameter order and Adam as tests/golden/reference_checkpoint.npz captured them)."""
 import pytest
 import torch
 
-from conftest import ROOT
+from conftest import load_golden
 
 from mri_interpolation_amd import checkpoint, models
-
-REF = os.environ.get("MRI_REFERENCE_DIR", "/root/reference")
 
 
 def _hash():
@@ -97,54 +91,62 @@ def test_layout_and_round_trip(tmp_path, build):
             assert torch.equal(m, moments[name][0]) and torch.equal(v, moments[name][1]), name
 
 
-@pytest.mark.skipif(not os.path.exists(os.path.join(REF, "models.py")),
-                    reason="the reference repository is only present in the build container")
+def _reference_stand_in(entry):
+    """A module with exactly the state-dict keys, shapes and parameter order of the reference's module
+    (tests/golden/reference_checkpoint.npz, captured from the reference classes by make_golden.py): what
+    `load_state_dict(strict=True)` and the optimiser's `load_state_dict` check of the reference module."""
+    root = torch.nn.Module()
+    params = set(entry["param_names"])
+    for key, shape in entry["state"]:
+        *path, leaf = key.split(".")
+        mod = root
+        for part in path:
+            if part not in mod._modules:
+                mod.add_module(part, torch.nn.Module())
+            mod = mod._modules[part]
+        if key in params:
+            mod.register_parameter(leaf, torch.nn.Parameter(torch.zeros(shape)))
+        else:
+            mod.register_buffer(leaf, torch.zeros(shape, dtype=torch.int64 if leaf == "num_batches_tracked"
+                                                  else torch.float32))
+    assert [n for n, _ in root.named_parameters()] == entry["param_names"]
+    return root
+
+
 @pytest.mark.parametrize("kind", ["hash", "siren"])
 def test_reference_classes_load_the_checkpoint_strictly(tmp_path, kind):
     """The file goes through `load_state_dict(strict=True)` of the reference's own HashMLP / SirenNet (what
     `load_from_checkpoint` does after Lightning's migration step) and its optimizer state through the
-    reference's `configure_optimizers()` Adam."""
-    # the reference's modules (`encoding`, `models`, its stand-ins) and its directory on sys.path must not
-    # outlive this test: later tests import this repository's `launcher`, `interp`, ...
-    saved_path, saved_modules = list(sys.path), set(sys.modules)
-    sys.path.insert(0, os.path.join(ROOT, "tests", "golden"))
-    try:
-        import make_golden
-        _, ref_models = make_golden.import_reference()
-        _check_reference_load(tmp_path, kind, ref_models)
-    finally:
-        sys.path[:] = saved_path
-        for name in set(sys.modules) - saved_modules:
-            mod = sys.modules[name]
-            from_ref = str(getattr(mod, "__file__", "") or "").startswith(REF)
-            stand_in = name.split(".")[0] in ("pytorch_lightning", "utils", "commentjson", "rff", "make_golden")
-            if from_ref or stand_in:
-                del sys.modules[name]
-
-
-def _check_reference_load(tmp_path, kind, ref_models):
+    reference's `configure_optimizers()` Adam -- both as the fixture captured them from the reference classes."""
+    fx = load_golden("reference_checkpoint")
+    entry = fx.meta[kind]
     if kind == "hash":
         model = _hash()
-        ref = ref_models.HashMLP(dim_in=3, dim_hidden=16, dim_out=1, n_layers=2, n_levels=3, n_features_per_level=2,
-                                 log2_hashmap_size=9, base_resolution=4, finest_resolution=32, lr=5e-3)
     else:
         model = _siren()
-        ref = ref_models.SirenNet(dim_in=3, dim_hidden=16, dim_out=1, n_layers=3, lr=1e-4)
+        # the parameters the reference's forward was evaluated on (a reference-layout state dict)
+        sd = {k: torch.from_numpy(fx[f"siren_sd_{i}"]) for i, (k, _) in enumerate(entry["state"])}
+        model.load_state_dict(sd)
+    ref = _reference_stand_in(entry)
     moments = _fake_moments(model, 12)
     path = str(tmp_path / "c.ckpt")
     torch.save(checkpoint.lightning_checkpoint(model, epoch=0, global_step=9, moments=moments, step=9), path)
     ckpt = torch.load(path, weights_only=True)
     result = ref.load_state_dict(ckpt["state_dict"], strict=True)
     assert not result.missing_keys and not result.unexpected_keys
-    x = torch.rand(7, 3)
     if kind == "siren":
-        model.cpu()
+        x = torch.from_numpy(fx["siren_x"])
+        for k, v in sd.items():
+            assert torch.equal(ckpt["state_dict"][k], v), k
         with torch.no_grad():  # same parameters: the reference's forward on them is the oracle's
             from oracle import mlp as omlp
-            params = [(l.weight, l.bias) for l in list(ref.layers) + [ref.last_layer]]
+            sdict = dict(ref.named_parameters())
+            params = [(sdict[w], sdict[b]) for w, b in entry["forward_layers"]]
             want = omlp.siren_forward(x, [(w.detach(), b.detach()) for w, b in params])
-            assert torch.allclose(ref(x), want, atol=1e-6)
-    opt = ref.configure_optimizers()
+            assert torch.allclose(torch.from_numpy(fx["siren_y"]), want, atol=1e-6)
+    o = entry["optimizer"]
+    opt = getattr(torch.optim, o["cls"])(ref.parameters(), lr=o["lr"], betas=tuple(o["betas"]), eps=o["eps"],
+                                         weight_decay=o["weight_decay"], amsgrad=o["amsgrad"])
     opt.load_state_dict(ckpt["optimizer_states"][0])
     ref_params = list(ref.parameters())
     names = [n for n, _ in ref.named_parameters()]

@@ -1,5 +1,7 @@
 """Host-side logic of the package (no GPU): level tables, NIfTI I/O, config, sharding,
 model surfaces and state-dict layout, launcher plumbing."""
+import gzip
+import hashlib
 import os
 
 import numpy as np
@@ -88,12 +90,17 @@ def test_nifti_round_trip_and_sample_slice(tmp_path):
     path = str(tmp_path / "s.nii.gz")
     nifti.save(raw, path)
     np.testing.assert_array_equal(nifti.load(path), raw.astype(np.float32))
-    sample = "/root/reference/sample_ankle_dyn_mri.nii.gz"
-    if os.path.exists(sample):  # only in the build container
-        full = nifti.load(sample)
-        assert full.shape == (352, 352, 6, 15)
-        want = (raw.astype(np.float64) * fx.meta["scl_slope"]).astype(np.float32)
-        np.testing.assert_array_equal(full[:, :, 3, 7], want)
+    # the reference's sample file itself, rebuilt byte for byte from its header and its voxels (fixtures)
+    hdr, vol = load_golden("sample_nifti_header"), load_golden("sample_volume")
+    data = hdr["header"].tobytes() + np.asarray(vol["raw_int16"], dtype="<i2").tobytes(order="F")
+    assert hashlib.sha256(data).hexdigest() == hdr.meta["sha256"]
+    sample = str(tmp_path / "sample_ankle_dyn_mri.nii.gz")
+    with gzip.open(sample, "wb") as f:
+        f.write(data)
+    full = nifti.load(sample)
+    assert full.shape == (352, 352, 6, 15)
+    want = (raw.astype(np.float64) * fx.meta["scl_slope"]).astype(np.float32)
+    np.testing.assert_array_equal(full[:, :, 3, 7], want)
 
 
 def test_config_defaults_and_json_mapping(tmp_path):

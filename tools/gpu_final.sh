@@ -6,10 +6,10 @@ o=gpurun_out/$MRI_ROUND/final; mkdir -p $o
 parts=${@:-bench prof pmc}   # (pmc2: only the FETCH / WRITE passes of cfg2 and cfg5)
 run() { local name=$1 limit=$2; shift 2; timeout -k 10 "$limit" "$@" > "$o/$name.json" 2> "$o/$name.err"; local rc=$?; echo "$name rc=$rc"; if [ $rc -eq 124 ] || [ $rc -eq 137 ]; then exit 1; fi; }
 if [[ $parts == *bench* ]]; then
-run bench_cfg4 600 python bench.py
-run bench_cfg2 300 python bench.py --workload cfg2
-run bench_cfg3 300 python bench.py --workload cfg3
-run bench_cfg5 300 python bench.py --workload cfg5
+run bench_cfg4 600 python bench.py --full
+run bench_cfg2 300 python bench.py --workload cfg2 --full
+run bench_cfg3 300 python bench.py --workload cfg3 --full
+run bench_cfg5 300 python bench.py --workload cfg5 --full
 run predict_cfg4 200 python bench.py --mode predict --steps 64
 run predict_cfg3 200 python bench.py --mode predict --workload cfg3 --steps 32
 run predict_cfg5 200 python bench.py --mode predict --workload cfg5 --steps 40

@@ -3,7 +3,7 @@
 export MRI_ROUND=r4
 o=gpurun_out/$MRI_ROUND/final; mkdir -p $o
 run() { local name=$1 limit=$2; shift 2; timeout -k 10 "$limit" "$@" > "$o/$name.json" 2> "$o/$name.err"; local rc=$?; echo "$name rc=$rc"; if [ $rc -eq 124 ] || [ $rc -eq 137 ]; then exit 1; fi; }
-run bench_cfg3 300 python bench.py --workload cfg3
+run bench_cfg3 300 python bench.py --workload cfg3 --full
 run predict_cfg3 200 python bench.py --mode predict --workload cfg3 --steps 32
 bash tools/gpu_prof.sh cfg3 --workload cfg3 --steps 20 --warmup 5 --no-records-leg > $o/prof_cfg3.log 2>&1 || exit 1; cp gpurun_out/$MRI_ROUND/cfg3_kernel_stats.csv $o/
 bash tools/gpu_pmc.sh cfg3_fetch "FETCH_SIZE" --workload cfg3 --steps 6 --warmup 2 --no-records-leg > $o/pmc_cfg3_fetch.log 2>&1 || exit 1

@@ -8,7 +8,7 @@ d=json.load(open(sys.argv[1]))
 print(sys.argv[1].split('/')[-1], round(d['ms_per_step'],4), d['phases_ms'], 'psnr', d.get('psnr'))
 PY
 }
-run() { name=$1; shift; timeout -k 10 200 python bench.py --no-records-leg --no-cpu-baseline --psnr-steps 500 "$@" > $o/$name.json 2> $o/$name.err; rc=$?; [ $rc -ne 0 ] && { echo "$name rc=$rc"; tail -3 $o/$name.err; }; [ $rc -eq 124 -o $rc -eq 137 ] && exit 1; line $o/$name.json; }
+run() { name=$1; shift; timeout -k 10 200 python bench.py --no-records-leg --no-cpu-baseline --psnr-steps 500 --full "$@" > $o/$name.json 2> $o/$name.err; rc=$?; [ $rc -ne 0 ] && { echo "$name rc=$rc"; tail -3 $o/$name.err; }; [ $rc -eq 124 -o $rc -eq 137 ] && exit 1; line $o/$name.json; }
 run new_a
 run old_a --opt mlp_x3=3
 run new_b
