@@ -396,6 +396,31 @@ int mri_siren_forward_loss(const float* x, const float* target, int64_t n, int64
                            float* d_b_last, float* loss_out, void* workspace,
                            int64_t workspace_bytes, void* stream);
 
+/* ---- PsfSirenNet: the acquisition point-spread function -----------------------------------
+ * (reference models.py:397-539.)  A target voxel b is the network averaged over S sample points around it:
+ * rows b*S + k of the expanded batch hold x[b] + offsets[k], and the voxel value is sum_k w_k z[b*S + k]
+ * (psf_conv, a Conv1d of kernel S and stride S).  1 <= S <= 4096, 1 <= dim_in (C) <= 8; every buffer is
+ * contiguous row-major.  Sums over the S samples of a target are owned by one wave (half-wave when S <= 32),
+ * taken in a fixed lane order in float64: results are bitwise reproducible and independent of the grid.
+ * mri_psf_expand (x_to_psf_x, models.py:520-526): x_psf (n*S, dim_in) = x.repeat_interleave(S, 0) +
+ *   offsets.repeat(n, 1), one f32 add per element (bit-exact); offsets (S, dim_in).
+ * mri_psf_reduce: out (n, C)[b, c] = sum_k w_k in[b*S + k, c]; w (S) or NULL for w_k = 1.  The Conv1d
+ *   forward (C = 1, models.py:535) and the backward of the expansion (C = dim_in, w = NULL).
+ * mri_psf_broadcast: dz (n*S)[b*S + k] = scale * w_k * g[b], the Conv1d's backward.
+ * mri_psf_mse_loss (training_step, models.py:529-537: psf_conv, then F.mse_loss(z, y)): zbar_out (n)
+ *   receives the reduced values, loss_out[0] += sum_b (zbar_b - y_b)^2 / n_total (ADDED; the caller zeroes),
+ *   dz (n*S) = w_k * 2 (zbar_b - y_b) / (n_total * grad_divisor) (written; NULL: no gradient).  n <= n_total:
+ *   a slice of n whole targets of a batch of n_total, as mri_siren_forward_loss. */
+int mri_psf_expand(const float* x, int64_t n, int32_t dim_in, const float* offsets, int32_t S,
+                   float* x_psf, void* stream);
+int mri_psf_reduce(const float* in, int64_t n, int32_t S, int32_t C, const float* w, float* out,
+                   void* stream);
+int mri_psf_broadcast(const float* g, int64_t n, int32_t S, const float* w, float scale, float* dz,
+                      void* stream);
+int mri_psf_mse_loss(const float* z, const float* target, int64_t n, int64_t n_total, int32_t S,
+                     const float* w, float grad_divisor, float* zbar_out, float* loss_out, float* dz,
+                     void* stream);
+
 /* ---- loss ------------------------------------------------------------------------------
  * F.mse_loss(y, y_pred) (reference models.py:64): loss_out[0] += mean((pred-target)^2)
  * (device scalar, caller zeroes), d_pred = 2 (pred - target) / (count * grad_divisor) if

@@ -72,6 +72,15 @@ def parse_args(argv=None):
     return p.parse_args(argv)
 
 
+def psf_spacing(shape, k, norm_siren=True):
+    """Default PsfSirenNet.coordinates_spacing: half the voxel pitch of each of the first k axes in the
+    loader's coordinates (linspace(lo, 1, s), lo = -1 under norm_siren, else 0): the PSF weights span +-0.5
+    voxel with a FWHM of one voxel, so offsets of +-half a pitch sample the grid they describe.  An axis of
+    one voxel gets 0."""
+    lo = -1.0 if norm_siren else 0.0
+    return tuple((1.0 - lo) / (s - 1) / 2 if s > 1 else 0.0 for s in list(shape)[:k])
+
+
 def build_model(config, models):
     """Instantiate `config.model_class`, passing only the keywords it accepts (Q5)."""
     import torch
@@ -89,6 +98,11 @@ def build_model(config, models):
             batch_norm=config.batch_norm)
         everything.pop("final_activation")
         everything["final_activation"] = config.final_activation_on
+    if config.model_class == "PsfSirenNet":
+        spacing = getattr(config, "coordinates_spacing", None)
+        if spacing is None:
+            spacing = psf_spacing(config.image_shape, min(3, config.dim_in), config.norm_siren)
+        everything.update(coordinates_spacing=spacing, n_sample=config.n_sample)
     params = inspect.signature(cls.__init__).parameters
     takes_kwargs = any(p.kind == p.VAR_KEYWORD for p in params.values())
     kwargs = {k: v for k, v in everything.items() if takes_kwargs or k in params}
@@ -155,7 +169,7 @@ def main(argv=None):
         raise SystemExit(f"base_resolution {config.base_resolution} does not match the "
                          f"{config.dim_in}-D volume (SURVEY.md Q7): pass --slice, --tiny_mlp or "
                          "--base_resolution / --finest_resolution with one value per axis")
-    config.norm_siren = config.model_class in ("SirenNet", "ModulatedSirenNet")
+    config.norm_siren = config.model_class in ("SirenNet", "ModulatedSirenNet", "PsfSirenNet")
     if use_cpu:
         return main_cpu(args, config, volume)
 

@@ -20,4 +20,7 @@ def __getattr__(name):
                 "nifti", "config"):
         import importlib
         return importlib.import_module("." + name, __name__)
+    if name == "PsfSirenNet":  # the one model class exported at the top (SIREN through the acquisition PSF)
+        from .models import PsfSirenNet
+        return PsfSirenNet
     raise AttributeError(name)

@@ -107,6 +107,10 @@ SIGNATURES = {
     "mri_siren_forward_loss": [_P, _P, _I64, _I64, _I32, _I32, _I32, C.POINTER(_P), C.POINTER(_P), _F,
                                _F, _F, C.POINTER(_P), C.POINTER(_P), _P, _P, _P, _P, _P, _P, _P,
                                _I64, _P],
+    "mri_psf_expand": [_P, _I64, _I32, _P, _I32, _P, _P],
+    "mri_psf_reduce": [_P, _I64, _I32, _I32, _P, _P, _P],
+    "mri_psf_broadcast": [_P, _I64, _I32, _P, _F, _P, _P],
+    "mri_psf_mse_loss": [_P, _P, _I64, _I64, _I32, _P, _F, _P, _P, _P, _P],
     "mri_adam_step": [_P, _P, _P, _P, _I64, _D, _D, _D, _D, _I32, _F, _P],
     "mri_sample_indices": [C.c_uint64, _I64, _I64, _I64, _I64, _P, _P],
     "mri_fused_step": [_P],

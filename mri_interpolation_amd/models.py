@@ -2,12 +2,16 @@
 
 Mirrors reference `models.py`: `BaseMLP` (models.py:20-95), `Sine` (:108-114), `SirenLayer`
 (:117-156), `SirenNet` (:160-233), `Modulator` / `ModulatedSirenNet` (:236-322), `HashMLP` (:658-754): same constructor arguments,
+`PsfSirenNet` (:397-539): same constructor arguments,
 `forward(x)`, `training_step`, `predict_step`, `configure_optimizers`, same state-dict keys.
 Known defects of the reference are resolved to the INTENDED semantics:
   Q1  HashMLP.forward applies the decoder blocks in sequence (the reference calls a ModuleList);
   Q2  BaseMLP.forward runs `self.layers(x)` (the reference recurses into itself);
   Q3  HashMLP does not build BaseMLP's unused default `layers` stack; checkpoints that carry
-      those dead `layers.*` keys still load.
+      those dead `layers.*` keys still load;
+  Q13 PsfSirenNet(coordinates_spacing=None) raises ValueError("No PSF spacing defined") (the reference's
+      `coordinates_spacing if not None else ValueError(...)` never raises, and its constructor then fails
+      inside torch.linspace).
 Every Linear(+activation) is one f32-MFMA kernel (csrc/linear.hip); there is no CPU path.
 """
 import math
@@ -368,3 +372,95 @@ class HashMLP(BaseMLP):
             state_dict.pop(key)
         super()._load_from_state_dict(state_dict, prefix, local_metadata, strict, missing_keys,
                                       unexpected_keys, error_msgs)
+
+
+def psf_table(coordinates_spacing, n_sample: int, dim_in: int):
+    """(offsets (S, dim_in), weights (S,)) of PsfSirenNet (reference models.py:449-508), S = n_sample^k for
+    k = len(coordinates_spacing) PSF axes: the first k input axes, the others get offset 0.  Built with the
+    reference's own torch ops (linspace, ij meshgrid, Gaussian of sigma 1 / 2.3548 on +-0.5, normalised to
+    sum 1): with k = dim_in = 3 the two tables are the reference's bit for bit."""
+    k = len(coordinates_spacing)
+    if not 1 <= k <= min(3, dim_in):
+        raise ValueError(f"coordinates_spacing needs 1 to min(3, dim_in = {dim_in}) values, got {k}")
+    axes = [torch.linspace(-coordinates_spacing[i], coordinates_spacing[i], n_sample) for i in range(k)]
+    grid = torch.stack(torch.meshgrid(*axes, indexing="ij"), dim=-1).reshape(-1, k)
+    offsets = torch.zeros(grid.shape[0], dim_in)
+    offsets[:, :k] = grid
+    sigma = 1.0 / 2.3548  # could be anisotropic to reflect MRI sequences (see Kainz et al.)
+
+    def gaussian(x, sigma):
+        return torch.exp(-x * x / (2 * sigma * sigma))
+
+    mesh = torch.meshgrid(*[torch.linspace(-0.5, 0.5, n_sample) for _ in range(k)], indexing="ij")
+    psf = gaussian(mesh[0], sigma)
+    for m in mesh[1:]:
+        psf = psf * gaussian(m, sigma)
+    psf = psf / torch.sum(psf)
+    return offsets, psf.flatten()
+
+
+class PsfSirenNet(SirenNet):
+    """SIREN trained through the acquisition PSF (reference models.py:397-539): a target voxel is the
+    network's Gaussian-weighted sum over S = n_sample^k points around it (x_to_psf_x, then psf_conv, a
+    Conv1d of kernel and stride S whose weight is fixed: `psf_conv.weight`, requires_grad=False, in the
+    state dict).  `forward` / `predict_step` are the plain SirenNet; only `training_step` sees the PSF.
+    coordinates_spacing: the offsets' half-width per PSF axis, k = 1 .. 3 values for the first k input axes
+    (the reference takes exactly 3 with dim_in = 3).  None raises (Q13).  Like the reference, the layers
+    use SirenLayer's default sigma 6."""
+
+    def __init__(self, dim_in: int = 3, dim_hidden: int = 64, dim_out: int = 1, n_layers: int = 4,
+                 w0: float = 30., w0_initial: float = 30., use_bias: bool = True, final_activation=None,
+                 lr: float = 1e-4, coordinates_spacing=None, n_sample: int = 5):
+        if coordinates_spacing is None:
+            raise ValueError("No PSF spacing defined")
+        if dim_out != 1:
+            raise ValueError(f"PsfSirenNet: dim_out must be 1 (psf_conv is a one-channel Conv1d), got {dim_out}")
+        if int(n_sample) < 1:
+            raise ValueError(f"n_sample must be >= 1, got {n_sample}")
+        offsets, psf = psf_table(coordinates_spacing, int(n_sample), dim_in)
+        super().__init__(dim_in=dim_in, dim_hidden=dim_hidden, dim_out=dim_out, n_layers=n_layers, w0=w0,
+                         w0_initial=w0_initial, use_bias=use_bias, final_activation=final_activation, lr=lr)
+        self.n_sample = int(n_sample)
+        self.coordinates_spacing = coordinates_spacing
+        self.psf_coordinates = offsets  # a plain attribute, as in the reference (not in the state dict)
+        self._psf_device = {}
+        psf_conv = nn.Conv1d(in_channels=1, out_channels=1, kernel_size=len(psf), stride=len(psf), padding=0,
+                             bias=False)  # holds the weight; its math runs in ops.psf_conv
+        psf_conv.weight = nn.Parameter(psf.unsqueeze(0).unsqueeze(0), requires_grad=False)
+        self.psf_conv = psf_conv
+
+    @property
+    def n_psf(self) -> int:
+        return self.psf_coordinates.shape[0]
+
+    def psf_offsets(self, device) -> torch.Tensor:
+        """psf_coordinates on `device` (uploaded once)."""
+        key = str(device)
+        t = self._psf_device.get(key)
+        if t is None:
+            t = self.psf_coordinates.to(device).contiguous()
+            self._psf_device[key] = t
+        return t
+
+    def psf_weights(self) -> torch.Tensor:
+        return self.psf_conv.weight.detach().reshape(-1)
+
+    def forward(self, x, mods=None):
+        return super().forward(x)
+
+    def x_to_psf_x(self, x: torch.Tensor):
+        """Row b S + k = x[b] + psf_coordinates[k] (reference models.py:520-526), one kernel."""
+        return ops.psf_expand_ad(x, self.psf_offsets(x.device))
+
+    def training_step(self, batch, batch_idx):
+        x, y = batch
+        z = self(self.x_to_psf_x(x))
+        z = ops.psf_conv(z, self.psf_conv.weight)
+        loss = self.criterion(y, z)
+        self.log("train_loss", loss)
+        return loss
+
+    def configure_optimizers(self):
+        # torch.optim.Adam skips psf_conv.weight (it never has a gradient); the flat buffers never take it
+        self.optimizer = optim.Adam([p for p in self.parameters() if p.requires_grad], lr=self.lr)
+        return self.optimizer

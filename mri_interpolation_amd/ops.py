@@ -710,6 +710,107 @@ class MSELossFunction(torch.autograd.Function):
         return d_pred * g, None
 
 
+# --------------------------------------------------------------------------- PsfSirenNet's PSF
+def _contiguous(*tensors):
+    for t in tensors:
+        if t is not None and not t.is_contiguous():
+            raise ValueError("the PSF ops need contiguous tensors")
+
+
+def psf_expand(x, offsets, out=None):
+    """x_psf (n S, dim_in): row b S + k = x[b] + offsets[k] (mri_psf_expand); offsets (S, dim_in)."""
+    _gpu(x, offsets, out)
+    _contiguous(x, offsets, out)
+    n, dim_in = x.shape
+    S = offsets.shape[0]
+    if offsets.shape[1] != dim_in:
+        raise ValueError(f"offsets {tuple(offsets.shape)} do not match x {tuple(x.shape)}")
+    if out is None:
+        out = torch.empty((n * S, dim_in), device=x.device, dtype=torch.float32)
+    elif out.shape != (n * S, dim_in):
+        raise ValueError(f"out {tuple(out.shape)}: expected {(n * S, dim_in)}")
+    _lib.call("mri_psf_expand", _ptr(x), n, dim_in, _ptr(offsets), S, _ptr(out), _stream())
+    return out
+
+
+def psf_reduce(x, S: int, w=None, out=None):
+    """out (n, C)[b] = sum_k w_k x[b S + k] for x (n S, C); w (S,) or None for ones (mri_psf_reduce)."""
+    _gpu(x, w, out)
+    _contiguous(x, w, out)
+    rows, C = x.shape
+    if rows % S:
+        raise ValueError(f"{rows} rows are not whole groups of S = {S}")
+    if w is not None and w.numel() != S:
+        raise ValueError(f"w has {w.numel()} values, S = {S}")
+    n = rows // S
+    if out is None:
+        out = torch.empty((n, C), device=x.device, dtype=torch.float32)
+    _lib.call("mri_psf_reduce", _ptr(x), n, S, C, _ptr(w), _ptr(out), _stream())
+    return out
+
+
+def psf_broadcast(g, S: int, w, scale: float = 1.0, out=None):
+    """dz (n S, 1)[b S + k] = scale w_k g[b] for g (n, 1) (mri_psf_broadcast)."""
+    _gpu(g, w, out)
+    _contiguous(g, w, out)
+    n = g.numel()
+    if w.numel() != S:
+        raise ValueError(f"w has {w.numel()} values, S = {S}")
+    if out is None:
+        out = torch.empty((n * S, 1), device=g.device, dtype=torch.float32)
+    _lib.call("mri_psf_broadcast", _ptr(g), n, S, _ptr(w), float(scale), _ptr(out), _stream())
+    return out
+
+
+def psf_mse_loss(z, target, S: int, w, loss_out, zbar, dz=None, n_total=None, grad_divisor: float = 1.0):
+    """Training loss of PsfSirenNet (mri_psf_mse_loss): zbar (n) = PSF-weighted sums of z (n S),
+    loss_out[0] += sum (zbar - target)^2 / n_total, dz = w_k 2 (zbar_b - target_b) / (n_total divisor)."""
+    _gpu(z, target, w, loss_out, zbar, dz)
+    _contiguous(z, target, w, zbar, dz)
+    n = target.numel()
+    if z.numel() != n * S or zbar.numel() != n or (dz is not None and dz.numel() != n * S) or w.numel() != S:
+        raise ValueError(f"psf_mse_loss: z / dz (n S), target / zbar (n), w (S) with n = {n}, S = {S}")
+    _lib.call("mri_psf_mse_loss", _ptr(z), _ptr(target), n, n if n_total is None else int(n_total), S,
+              _ptr(w), float(grad_divisor), _ptr(zbar), _ptr(loss_out), _ptr(dz), _stream())
+    return loss_out
+
+
+class PsfExpandFunction(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, offsets):
+        ctx.S = offsets.shape[0]
+        return psf_expand(x.contiguous(), offsets.contiguous())
+
+    @staticmethod
+    def backward(ctx, g):
+        if not ctx.needs_input_grad[0]:
+            return None, None
+        return psf_reduce(g.contiguous(), ctx.S), None
+
+
+class PsfConvFunction(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, z, w):
+        w = w.detach().reshape(-1).contiguous()
+        ctx.save_for_backward(w)
+        return psf_reduce(z.contiguous().reshape(-1, 1), w.numel(), w)
+
+    @staticmethod
+    def backward(ctx, g):
+        (w,) = ctx.saved_tensors
+        return psf_broadcast(g.contiguous(), w.numel(), w), None
+
+
+def psf_expand_ad(x, offsets):
+    """Differentiable psf_expand (its backward sums the S rows of each target)."""
+    return PsfExpandFunction.apply(x, offsets)
+
+
+def psf_conv(z, w):
+    """psf_conv(z.T).T of the reference: (n S, 1) -> (n, 1) with the fixed PSF weights w."""
+    return PsfConvFunction.apply(z, w)
+
+
 def adam_step(param, grad, exp_avg, exp_avg_sq, lr, beta1, beta2, eps, step,
               grad_scale: float = 1.0):
     _gpu(param, grad, exp_avg, exp_avg_sq)

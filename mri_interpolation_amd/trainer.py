@@ -67,10 +67,13 @@ def fusable_layers(model) -> Optional[tuple]:
 class FusedStep:
     """Explicit forward / backward kernel chain over preallocated workspaces."""
 
-    def __init__(self, model, optimizer: optim.Adam, world: int = 1):
+    def __init__(self, model, optimizer: optim.Adam, world: int = 1, psf_row_budget: int = 1 << 20):
         plan = fusable_layers(model)
         if plan is None:
             raise ValueError("model is not a fusable chain")
+        # PsfSirenNet: the chain's training step runs on the n S expanded rows, and the loss is taken
+        # through the PSF (_psf_pass); at most psf_row_budget expanded rows are in flight at once
+        self.psf_row_budget = int(psf_row_budget)
         self.encoder, self.layers = plan
         if self.encoder is not None and getattr(self.encoder, "_too_fine", False):
             raise OverflowError("int too big to convert")  # what encoder.forward raises
@@ -89,6 +92,7 @@ class FusedStep:
         self.use_tiny = self.tiny is not None
         self.chain = self._siren_chain_plan()
         self.use_chain = self.chain is not None
+        self.psf = self._psf_plan(model)
         # train_step folds the loss and the head's backward into the forward kernel (needs a
         # sine layer below the last one); forward() + backward() keep the separate kernels
         self.chain_loss = self.use_chain and len(self.layers) >= 3
@@ -208,6 +212,55 @@ class FusedStep:
         return dict(weights=[l.weight.data for l in ls], biases=[l.bias.data for l in ls],
                     w0_first=ls[0].w0, w0=ls[1].w0 if len(ls) > 2 else ls[0].w0,
                     d_weights=[g[0] for g in self._grads], d_biases=[g[1] for g in self._grads])
+
+    def _psf_plan(self, model):
+        """PsfSirenNet: S, the offset table and the PSF weights beside the chain plan.  Without the chain
+        kernels (e.g. dim_hidden 352) there is no fused PSF step: the model trains through training_step."""
+        if not isinstance(model, models.PsfSirenNet):
+            return None
+        if not self.use_chain:
+            raise ValueError("PsfSirenNet: the fused PSF step needs the SIREN chain kernels "
+                             "(training_step + autograd trains the other shapes)")
+        dev = self.flat.param.device
+        return dict(S=model.n_psf, offsets=model.psf_offsets(dev), w=model.psf_weights(),
+                    zbar=None, x_psf=None)
+
+    def _psf_pass(self, coords, target, first, divisor):
+        """PsfSirenNet's training step, cut into chunks of whole targets of at most psf_row_budget expanded
+        rows: expand -> chain forward (training form) -> PSF-weighted MSE and its gradient -> chain
+        backward.  Gradients add over the chunks; n_total keeps the loss and the gradient a mean over the
+        whole batch."""
+        p, c, n_sine = self.psf, self.chain, len(self.layers) - 1
+        n, dim_in, S = coords.shape[0], coords.shape[1], self.psf["S"]
+        per = max(1, min(n, self.psf_row_budget // S))
+        ws = self._workspace(per * S, True)
+        if p["x_psf"] is None or p["x_psf"].shape[0] < per * S:
+            p["x_psf"] = torch.empty((per * S, dim_in), device=coords.device, dtype=torch.float32)
+        if p["zbar"] is None or p["zbar"].shape[0] < per:
+            p["zbar"] = torch.empty(per, device=coords.device, dtype=torch.float32)
+        with self._phase("zero_grad"):
+            if first:
+                self.flat.grad.zero_()
+            self.loss.zero_()
+        coords, target = coords.contiguous(), target.reshape(-1).contiguous()
+        for lo in range(0, n, per):
+            m = min(per, n - lo)
+            rows = m * S
+            xp = p["x_psf"][:rows]
+            act = [t[:rows] for t in ws["y"][:n_sine]]
+            deriv = [t[:rows] for t in ws["deriv"][:n_sine]]
+            y, dz = ws["y"][-1][:rows], ws["dz"][-1][:rows]
+            with self._phase("psf_expand"):
+                ops.psf_expand(coords[lo:lo + m], p["offsets"], out=xp)
+            with self._phase("mlp_fwd"):
+                ops.siren_forward(xp, c["weights"], c["biases"], c["w0_first"], c["w0"], act=act, deriv=deriv,
+                                  y=y)
+            with self._phase("loss"):
+                ops.psf_mse_loss(y, target[lo:lo + m], S, p["w"], self.loss, p["zbar"][:m], dz, n_total=n,
+                                 grad_divisor=float(self.world) * float(divisor))
+            with self._phase("mlp_bwd"):
+                ops.siren_backward(xp, dz, c["weights"], act, deriv, [None] + [t[:rows] for t in ws["dz"][1:n_sine]],
+                                   c["d_weights"], c["d_biases"])
 
     @contextlib.contextmanager
     def _phase(self, name: str):
@@ -482,6 +535,8 @@ class FusedStep:
         is started afresh (zeroed / overwritten), else added to; `step`: this call completes the
         gradient (data parallel: start its reductions); gradients are scaled by
         1 / (world * divisor)."""
+        if self.psf is not None:
+            raise RuntimeError("PsfSirenNet: its loss is taken through the PSF, train with train_step")
         div = float(self.world) * float(divisor)
         if self.use_tiny:
             # every gradient (tables, decoder) and the loss are OVERWRITTEN by the two kernels
@@ -655,7 +710,10 @@ class FusedStep:
 
                 late, late_work = late_work, None
                 queue_side()
-        if self.use_chain and self.chain_loss:
+        if self.psf is not None:
+            self._pending = []
+            self._psf_pass(coords, target, first, divisor)
+        elif self.use_chain and self.chain_loss:
             self._pending = []
             self._chain_loss_pass(coords, target, first, divisor)
         else:
@@ -744,6 +802,8 @@ class SteadyLoop:
     @staticmethod
     def unsupported(step: "FusedStep", pipe: BatchPipeline) -> Optional[str]:
         ld = pipe.loader
+        if step.psf is not None:
+            return "PsfSirenNet: the PSF step runs eagerly (FusedStep.train_step), it has no native form"
         if step.world != 1 and (step.dp_mode != "all_reduce" or step.grad_buckets > 1):
             return "several ranks: the plain all-reduce form only (one reduction of the flat gradient)"
         if not (step.use_tiny and step.encoder is not None):
