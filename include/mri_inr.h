@@ -67,20 +67,40 @@ typedef struct mri_grid_desc {
 /* Library / build identification: "mri_inr <version> gfx950". */
 const char* mri_version(void);
 const char* mri_last_error(void);
-/* Speed-only tuning knobs ("xcd_affinity" 0/1, "bwd_lds_max_parts" n, "bwd_blocks_per_level" n,
- * "bwd_dense_max_parts" n, "bwd_dense_blocks" n, "bwd_fuse_dense" 0/1, "fwd_pair" 0/1,
- * "mlp_stagger" 0..8, "mlp_x3" 0/1/2: which kernel serves the decoder -- 1 (default) the bf16-pipe
- * kernel with exact three-term operands, 2 its four-wave form (128-wide), 0 the f32-MFMA kernels;
- * "siren_rows" 0/1: SirenNet of width 256 -- 1 (default) the chain kernels that keep a wave's rows in
- * registers across the layers (csrc/siren_rows.hip), 0 the LDS-image kernels of every other width);
- * results stay within fp32 summation-order noise.
+/* Tuning knobs, process-wide, read when a call plans its launches.  Defaults in parentheses.
+ * Speed-only knobs whose results are BITWISE those of the default (tests/test_gpu_knobs.py):
+ *   "xcd_affinity" 0/1 (1): block -> level map of the hash-grid forward (and of the global-atomic
+ *   backward, whose f32 atomics add in no fixed order whatever the map);
+ *   table-gradient knobs of the binned path (methods 0 / 2, every contribution is one f32 product turned
+ *   into fixed point and the sums are int64, so how the work is cut changes no bit):
+ *   "bwd_dense_max_parts" n (4): levels of at most n table slices skip the records (dense path);
+ *   "bwd_fuse_dense" 0/1 (1): the dense levels share the launch of the record accumulation;
+ *   "bwd_dense_blocks" n >= 1 (96), "bwd_blocks_per_level" n >= 1 (64): workgroups of the dense levels /
+ *   per binned level (values below 1 are stored as 1);
+ *   "mlp_stagger" 0..8 (0): segments team 1 of the 128-wide f32-MFMA decoder runs behind team 0
+ *   (other values are rejected).
+ * Speed-only knobs that keep results within fp32 summation-order noise:
+ *   "fwd_pair" 0/1 (1): F = 2 forward, two lanes per (coordinate, level) with the partial sums added last,
+ *   or one lane adding the corners in order;
+ *   "bwd_lds_max_parts" n (256): under method 0, levels of more than n slices take global f32 atomics;
+ *   "mlp_x3" 0/1/2 (1): which kernel serves the decoder -- 1 the bf16-pipe kernel with exact three-term
+ *   operands, 2 its four-wave form (128-wide), 0 the f32-MFMA kernels;
+ *   "siren_rows" 0/1 (1): SirenNet of width 256 -- 1 the chain kernels that keep a wave's rows in
+ *   registers across the layers (csrc/siren_rows.hip), 0 the LDS-image kernels of every other width.
+ * 0/1 knobs store any nonzero value as 1.  The workspace size and the plan of the table-gradient backward
+ * depend on the knobs: they must not change between mri_hashgrid_backward_workspace_bytes /
+ * mri_hashgrid_backward_prepare and the backward calls that use that workspace, nor during the life of a
+ * fused training step (its count-ahead stage prepares the next step's backward).
  * ONE option trades accuracy, for grids with two features per level: "bwd_records" 0 (default) / 1,
  * the gradient records of mri_hashgrid_backward* (see there).  0: every contribution w * g is the f32
  * product the reference's autograd forms, their sum per table entry is exact.  1: each contribution is
  * rounded to 18-21 significant bits (8-byte packed records) before the exact sum -- 13 us faster per
  * step at BASELINE config 4 and NOT f32-equivalent (per table entry 17x the median error of the f32
- * records against float64, tests/test_gpu_round3.py). */
+ * records against float64, tests/test_gpu_round3.py).  Other values are rejected.
+ * Both calls return MRI_ERR_INVALID_ARGUMENT for an unknown name. */
 int mri_set_option(const char* name, int32_t value);
+/* The current value of a knob (HOST pointer), as mri_set_option stored it. */
+int mri_get_option(const char* name, int32_t* value);
 
 /* ---- hash-grid encoding --------------------------------------------------------------
  * Replaces, per level, the op chain of _HashGrid.forward / _HashGridV2.forward

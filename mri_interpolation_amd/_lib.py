@@ -64,6 +64,7 @@ _D = C.c_double
 # name -> argtypes; every function returns int except the two string getters
 SIGNATURES = {
     "mri_set_option": [C.c_char_p, _I32],
+    "mri_get_option": [C.c_char_p, C.POINTER(_I32)],
     "mri_hashgrid_forward": [C.POINTER(GridDesc), _P, _I64, _P, _P, _I64, _I64, _I64, _P],
     "mri_hashgrid_backward": [C.POINTER(GridDesc), _P, _P, _I64, _I64, _I64, _I64, _P, _I32, _P,
                               _I64, _P],
@@ -163,6 +164,13 @@ def load():
     for name, argtypes in INT_GETTERS.items():
         getattr(lib, name).restype = C.c_int
         getattr(lib, name).argtypes = argtypes
+    # mri_fused_step reads the struct the trainer fills in: a library built from another header would
+    # read past (or short of) it without any error
+    lib_bytes, py_bytes = lib.mri_fused_step_args_bytes(), C.sizeof(FusedStepArgs)
+    if lib_bytes != py_bytes:
+        raise RuntimeError(
+            f"stale libmri_inr.so at {_LIB_PATH}: its mri_fused_step_args is {lib_bytes} bytes, the "
+            f"binding's FusedStepArgs {py_bytes}; rebuild with `python -m mri_interpolation_amd.build`")
     _lib = lib
     return lib
 
@@ -183,3 +191,9 @@ def version() -> str:
 
 def set_option(name: str, value: int):
     call("mri_set_option", name.encode(), int(value))
+
+
+def get_option(name: str) -> int:
+    value = _I32()
+    check(load().mri_get_option(name.encode(), C.byref(value)), "mri_get_option")
+    return value.value

@@ -237,34 +237,54 @@ using namespace mri;
 extern "C" const char* mri_version(void) { return "mri_inr 0.1.0 gfx950"; }
 extern "C" const char* mri_last_error(void) { return error_buffer(); }
 
+namespace {
+// name -> field of Options: the one list mri_set_option and mri_get_option look names up in
+int* option_field(const char* name) {
+  Options& o = options();
+  const struct {
+    const char* name;
+    int* field;
+  } fields[] = {{"xcd_affinity", &o.xcd_affinity},
+                {"bwd_lds_max_parts", &o.bwd_lds_max_parts},
+                {"bwd_blocks_per_level", &o.bwd_blocks_per_level},
+                {"fwd_pair", &o.fwd_pair},
+                {"mlp_stagger", &o.mlp_stagger},
+                {"mlp_x3", &o.mlp_x3},
+                {"bwd_fuse_dense", &o.bwd_fuse_dense},
+                {"bwd_dense_blocks", &o.bwd_dense_blocks},
+                {"bwd_dense_max_parts", &o.bwd_dense_max_parts},
+                {"bwd_records", &o.bwd_records},
+                {"siren_rows", &o.siren_rows}};
+  for (const auto& f : fields)
+    if (!strcmp(name, f.name)) return f.field;
+  return nullptr;
+}
+}  // namespace
+
 extern "C" int mri_set_option(const char* name, int32_t value) {
   MRI_REQUIRE(name != nullptr, "option name is NULL");
-  if (!strcmp(name, "xcd_affinity")) {
-    options().xcd_affinity = value != 0;
-  } else if (!strcmp(name, "bwd_lds_max_parts")) {
-    options().bwd_lds_max_parts = value;
-  } else if (!strcmp(name, "bwd_fuse_dense")) {
-    options().bwd_fuse_dense = value != 0;
-  } else if (!strcmp(name, "bwd_dense_blocks")) {
-    options().bwd_dense_blocks = value < 1 ? 1 : value;
-  } else if (!strcmp(name, "bwd_dense_max_parts")) {
-    options().bwd_dense_max_parts = value;
-  } else if (!strcmp(name, "fwd_pair")) {
-    options().fwd_pair = value != 0;
-  } else if (!strcmp(name, "mlp_x3")) {
-    options().mlp_x3 = value;
-  } else if (!strcmp(name, "mlp_stagger")) {
-    options().mlp_stagger = value;
+  int* field = option_field(name);
+  if (!field) return fail(MRI_ERR_INVALID_ARGUMENT, "unknown option '%s'", name);
+  if (!strcmp(name, "xcd_affinity") || !strcmp(name, "bwd_fuse_dense") || !strcmp(name, "fwd_pair") ||
+      !strcmp(name, "siren_rows")) {
+    value = value != 0;
+  } else if (!strcmp(name, "bwd_dense_blocks") || !strcmp(name, "bwd_blocks_per_level")) {
+    value = value < 1 ? 1 : value;
   } else if (!strcmp(name, "bwd_records")) {
     MRI_REQUIRE(value == 0 || value == 1, "bwd_records %d not in {0, 1}", value);
-    options().bwd_records = value;
-  } else if (!strcmp(name, "siren_rows")) {
-    options().siren_rows = value != 0;
-  } else if (!strcmp(name, "bwd_blocks_per_level")) {
-    options().bwd_blocks_per_level = value < 1 ? 1 : value;
-  } else {
-    return fail(MRI_ERR_INVALID_ARGUMENT, "unknown option '%s'", name);
+  } else if (!strcmp(name, "mlp_stagger")) {
+    // the team kernel pairs team 1's leading barriers with team 0's trailing ones: at most 8
+    MRI_REQUIRE(value >= 0 && value <= 8, "mlp_stagger %d not in 0..8", value);
   }
+  *field = value;
+  return MRI_OK;
+}
+
+extern "C" int mri_get_option(const char* name, int32_t* value) {
+  MRI_REQUIRE(name != nullptr && value != nullptr, "option name or value pointer is NULL");
+  const int* field = option_field(name);
+  if (!field) return fail(MRI_ERR_INVALID_ARGUMENT, "unknown option '%s'", name);
+  *value = *field;
   return MRI_OK;
 }
 

@@ -7,6 +7,7 @@ import re
 import pytest
 
 from conftest import ROOT
+from yardstick import KNOB_DEFAULTS
 
 HEADER = os.path.join(ROOT, "include", "mri_inr.h")
 
@@ -114,3 +115,87 @@ def test_missing_library_fails_loudly(lib, monkeypatch):
     monkeypatch.setattr(lib, "_LIB_PATH", "/nonexistent/libmri_inr.so")
     with pytest.raises(RuntimeError, match="no CPU/PyTorch fallback"):
         lib.load()
+
+
+def _get(h, name):
+    v = C.c_int32(-12345)
+    rc = h.mri_get_option(name.encode(), C.byref(v))
+    return rc, v.value
+
+
+def test_option_defaults_round_trips_and_clamps(lib):
+    h = lib.load()
+    # the header names every knob this list holds, with its default
+    text = open(HEADER).read()
+    for name, value in KNOB_DEFAULTS.items():
+        assert f'"{name}"' in text, name
+        assert _get(h, name) == (0, value), name
+        assert lib.get_option(name) == value
+    try:
+        # plain integers are stored as given
+        for name in ("bwd_lds_max_parts", "bwd_dense_max_parts"):
+            for v in (0, 1, 8, 1 << 30, -3):
+                assert h.mri_set_option(name.encode(), v) == 0
+                assert _get(h, name) == (0, v), (name, v)
+        for v in (0, 1, 2):
+            assert h.mri_set_option(b"mlp_x3", v) == 0 and _get(h, "mlp_x3") == (0, v)
+        # 0/1 switches store any nonzero value as 1
+        for name in ("xcd_affinity", "bwd_fuse_dense", "fwd_pair", "siren_rows"):
+            for v, want in ((0, 0), (1, 1), (7, 1), (-1, 1), (0, 0)):
+                assert h.mri_set_option(name.encode(), v) == 0
+                assert _get(h, name) == (0, want), (name, v)
+        # workgroup counts are at least 1
+        for name in ("bwd_dense_blocks", "bwd_blocks_per_level"):
+            for v, want in ((7, 7), (4096, 4096), (1, 1), (0, 1), (-5, 1)):
+                assert h.mri_set_option(name.encode(), v) == 0
+                assert _get(h, name) == (0, want), (name, v)
+        # values that cannot be served are rejected and leave the knob as it was
+        for v in range(0, 9):
+            assert h.mri_set_option(b"mlp_stagger", v) == 0 and _get(h, "mlp_stagger") == (0, v)
+        for v in (-1, 9, 1 << 20):
+            assert h.mri_set_option(b"mlp_stagger", v) == -1
+            assert "mlp_stagger" in h.mri_last_error().decode()
+            assert _get(h, "mlp_stagger") == (0, 8)
+        assert h.mri_set_option(b"bwd_records", 1) == 0 and _get(h, "bwd_records") == (0, 1)
+        for v in (-1, 2):
+            assert h.mri_set_option(b"bwd_records", v) == -1
+            assert _get(h, "bwd_records") == (0, 1)
+    finally:
+        for name, value in KNOB_DEFAULTS.items():
+            lib.set_option(name, value)
+    assert {name: lib.get_option(name) for name in KNOB_DEFAULTS} == KNOB_DEFAULTS
+    # unknown names and NULL pointers: -1 with a message, nothing written
+    v = C.c_int32(77)
+    assert h.mri_get_option(b"no_such_option", C.byref(v)) == -1 and v.value == 77
+    assert "no_such_option" in h.mri_last_error().decode()
+    assert h.mri_get_option(None, C.byref(v)) == -1 and v.value == 77
+    assert h.mri_get_option(b"fwd_pair", None) == -1
+    assert h.mri_set_option(None, 0) == -1
+    with pytest.raises(RuntimeError, match="unknown option"):
+        lib.get_option("bogus")
+
+
+def test_fused_step_args_layout_matches_the_library(lib):
+    h = lib.load()
+    assert h.mri_fused_step_args_bytes() == C.sizeof(lib.FusedStepArgs)
+
+
+def test_stale_library_layout_is_refused(lib, monkeypatch):
+    """A library whose mri_fused_step_args differs from the binding's struct (built from an older
+    header) must not load: mri_fused_step would read past the struct the trainer fills in."""
+    real = lib.load()
+
+    class Stale:  # the real library, but for the size it reports
+        def __init__(self, path):
+            self.mri_fused_step_args_bytes = lambda: C.sizeof(lib.FusedStepArgs) + 8
+
+        def __getattr__(self, name):
+            return getattr(real, name)
+
+    monkeypatch.setattr(lib, "_lib", None)
+    monkeypatch.setattr(lib.C, "CDLL", Stale)
+    with pytest.raises(RuntimeError, match="stale libmri_inr.so.*rebuild"):
+        lib.load()
+    assert lib._lib is None
+    monkeypatch.undo()
+    assert lib.load() is real

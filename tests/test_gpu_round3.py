@@ -15,6 +15,7 @@ import pytest
 import torch
 
 from conftest import REL_TOL, ROOT, assert_close, load_golden
+from yardstick import cfg4_gradient_case as _cfg4_gradient_case
 from oracle import detrand
 from oracle import hashgrid as ohash
 from oracle import mlp as omlp
@@ -45,15 +46,6 @@ def _report(name, payload):
 
 
 # --------------------------------------------------------------------------- record formats
-def _cfg4_gradient_case(n, seed):
-    """Coordinates and an incoming gradient d_enc whose magnitudes spread over ~12 binades per level
-    (as the decoder's do: a few coordinates carry most of the loss)."""
-    x = torch.from_numpy(detrand.uniform(n * 3, seed, 0.0, 1.0).reshape(n, 3))
-    g = torch.from_numpy(detrand.uniform(n * 32, seed + 1, -1.0, 1.0).reshape(n, 32))
-    spread = torch.from_numpy(detrand.uniform(n, seed + 2, -6.0, 2.0).reshape(n, 1))
-    return x, (g * torch.exp2(spread) * 1e-5).float()
-
-
 def _per_slot_stats(got, total, mag, floor):
     """max, rms and median of |got - exact| / |exact| over the slots whose exact value is above `floor`."""
     sel = total.abs() > floor

@@ -8,8 +8,10 @@ inputs: the claim under test is "the kernel is no worse an f32 evaluation than t
 import os
 
 import numpy as np
+import torch
 
 from conftest import rel_err
+from oracle import detrand
 
 # A kernel within 1e-6 of the float64 result passes whatever the reference does: torch's CPU sums are
 # cascaded and land within ~1e-7 of exact on a well-conditioned tensor (config 3's bias gradients: 1.0e-7
@@ -39,3 +41,18 @@ def assert_no_worse(kernel, f32_ref, f64, what="", factor=2.0, floor=FLOOR, max_
         (f"{what}: kernel is {k_max:.3e} (max) / {k_l2:.3e} (L2) from float64, the f32 reference "
          f"{r_max:.3e} / {r_l2:.3e}")
     return k_max, r_max
+
+
+def cfg4_gradient_case(n, seed):
+    """Coordinates (n, 3) and an incoming gradient d_enc (n, 32) of BASELINE config 4 whose magnitudes
+    spread over ~12 binades per level (as the decoder's do: a few coordinates carry most of the loss)."""
+    x = torch.from_numpy(detrand.uniform(n * 3, seed, 0.0, 1.0).reshape(n, 3))
+    g = torch.from_numpy(detrand.uniform(n * 32, seed + 1, -1.0, 1.0).reshape(n, 32))
+    spread = torch.from_numpy(detrand.uniform(n, seed + 2, -6.0, 2.0).reshape(n, 1))
+    return x, (g * torch.exp2(spread) * 1e-5).float()
+
+
+# Documented defaults of the library's tuning knobs (csrc/common.h struct Options, include/mri_inr.h).
+KNOB_DEFAULTS = {"xcd_affinity": 1, "bwd_lds_max_parts": 256, "bwd_blocks_per_level": 64, "fwd_pair": 1,
+                 "mlp_stagger": 0, "mlp_x3": 1, "bwd_fuse_dense": 1, "bwd_dense_blocks": 96,
+                 "bwd_dense_max_parts": 4, "bwd_records": 0, "siren_rows": 1}
