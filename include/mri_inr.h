@@ -441,6 +441,37 @@ int mri_psf_mse_loss(const float* z, const float* target, int64_t n, int64_t n_t
                      const float* w, float grad_divisor, float* zbar_out, float* loss_out, float* dz,
                      void* stream);
 
+/* ---- BatchNorm1d + activation (the default HashMLP decoder block) ----------------------------
+ * (torch.nn.BatchNorm1d as used at reference models.py:728-737: Linear -> BatchNorm1d -> GELU -> Dropout(0).)
+ * z (n, C) float32 row-major with a leading dimension, 1 <= C <= 1024; training needs n >= 2.  Every
+ * per-feature sum is taken in float64 in an order fixed by (n, C, 16-byte alignment of the matrices) alone --
+ * contiguous row chunks, a fixed tree inside a chunk, the chunk sums added in a fixed order, no atomics:
+ * bitwise reproducible.  `workspace`: mri_bn_workspace_bytes(n, C) bytes, 16-byte aligned, shared by
+ * mri_bn_stats and mri_bn_act_backward (the backward leaves two batch means in it between its kernels).
+ * mri_bn_stats (BatchNorm1d.forward in train(), the statistics): save (2, C) = batch mean and
+ *   invstd = 1 / sqrt(var + eps) with the BIASED variance (sums of z - z[0, c] and its square: exact in
+ *   float64 whatever the mean); running_mean = (1 - momentum) running_mean + momentum mean, running_var
+ *   likewise with the UNBIASED variance var n / (n - 1), num_batches_tracked[0] += 1 (int64, on the
+ *   device).  Any of the three buffers may be NULL (not tracked).
+ * mri_bn_act_forward: y = act(gamma * ((z - mean) * invstd) + beta), act one of MRI_ACT_IDENTITY / RELU /
+ *   GELU.  save != NULL: the batch statistics of mri_bn_stats (training); save == NULL: the eval form
+ *   with running_mean and invstd = 1 / sqrt(running_var + eps); no buffer is written.  y may be z.
+ * mri_bn_act_backward (autograd of the same): g = dy * act'(u), dbeta = sum g, dgamma = sum g xhat,
+ *   dz = gamma invstd (g - dbeta / n - xhat dgamma / n); xhat and u are recomputed from z and save with the
+ *   forward's expressions (nothing else is kept for the backward).  d_gamma / d_beta are written
+ *   (overwrite != 0) or added to; dz may alias dy (same leading dimension), not z. */
+int64_t mri_bn_workspace_bytes(int64_t n, int32_t C);
+int mri_bn_stats(const float* z, int64_t ldz, int64_t n, int32_t C, double momentum, double eps,
+                 float* running_mean, float* running_var, int64_t* num_batches_tracked, float* save,
+                 void* workspace, int64_t workspace_bytes, void* stream);
+int mri_bn_act_forward(const float* z, int64_t ldz, int64_t n, int32_t C, const float* save,
+                       const float* running_mean, const float* running_var, double eps, const float* gamma,
+                       const float* beta, int32_t activation, float* y, int64_t ldy, void* stream);
+int mri_bn_act_backward(const float* dy, int64_t lddy, const float* z, int64_t ldz, int64_t n, int32_t C,
+                        const float* save, const float* gamma, const float* beta, int32_t activation,
+                        float* dz, int64_t lddz, float* d_gamma, float* d_beta, int32_t overwrite,
+                        void* workspace, int64_t workspace_bytes, void* stream);
+
 /* ---- loss ------------------------------------------------------------------------------
  * F.mse_loss(y, y_pred) (reference models.py:64): loss_out[0] += mean((pred-target)^2)
  * (device scalar, caller zeroes), d_pred = 2 (pred - target) / (count * grad_divisor) if

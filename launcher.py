@@ -49,6 +49,10 @@ def parse_args(argv=None):
     p.add_argument("--finest_resolution", type=str, help="as --base_resolution (floats allowed)")
     p.add_argument("--tiny_mlp", action="store_true",
                    help="HashMLP with the fused ReLU tiny-MLP decoder of hash_config.json")
+    p.add_argument("--fused_batchnorm", action="store_true",
+                   help="HashMLP with the reference's BatchNorm decoder (the default model): train and predict "
+                        "through the fused BatchNorm kernel chain instead of training_step + autograd; on this "
+                        "path predict does not collect model.latents (as on the other fused paths)")
     p.add_argument("--holdout_odd_frames", action="store_true",
                    help="train on the even frames of the last axis, report PSNR on the odd ones "
                         "(BASELINE config 5 protocol)")
@@ -198,7 +202,8 @@ def main(argv=None):
     # ---- training -------------------------------------------------------------------------
     trainer = Trainer(max_epochs=config.epochs, max_steps=args.max_steps, precision=32,
                       log_every=args.log_every,
-                      accumulate_grad_batches=config.accumulate_grad_batches)
+                      accumulate_grad_batches=config.accumulate_grad_batches,
+                      fused_batchnorm=args.fused_batchnorm)
     t0 = time.time()
     trainer.fit(model, train_loader)
     train_seconds = time.time() - t0

@@ -112,6 +112,10 @@ SIGNATURES = {
     "mri_psf_reduce": [_P, _I64, _I32, _I32, _P, _P, _P],
     "mri_psf_broadcast": [_P, _I64, _I32, _P, _F, _P, _P],
     "mri_psf_mse_loss": [_P, _P, _I64, _I64, _I32, _P, _F, _P, _P, _P, _P],
+    "mri_bn_stats": [_P, _I64, _I64, _I32, _D, _D, _P, _P, _P, _P, _P, _I64, _P],
+    "mri_bn_act_forward": [_P, _I64, _I64, _I32, _P, _P, _P, _D, _P, _P, _I32, _P, _I64, _P],
+    "mri_bn_act_backward": [_P, _I64, _P, _I64, _I64, _I32, _P, _P, _P, _I32, _P, _I64, _P, _P, _I32, _P, _I64,
+                            _P],
     "mri_adam_step": [_P, _P, _P, _P, _I64, _D, _D, _D, _D, _I32, _F, _P],
     "mri_sample_indices": [C.c_uint64, _I64, _I64, _I64, _I64, _P, _P],
     "mri_fused_step": [_P],
@@ -121,6 +125,7 @@ STRING_GETTERS = ["mri_version", "mri_last_error"]
 INT64_GETTERS = {"mri_hashgrid_backward_workspace_bytes": [C.POINTER(GridDesc), _I64],
                  "mri_fused_step_args_bytes": [],
                  "mri_tiny_mlp_workspace_bytes": [_I32, _I32, _I64],
+                 "mri_bn_workspace_bytes": [_I64, _I32],
                  "mri_siren_backward_workspace_bytes": [_I64, _I32, _I32],
                  "mri_siren_forward_workspace_bytes": [_I32, _I32],
                  "mri_hashgrid_forward_signal_blocks": [C.POINTER(GridDesc), _I64],

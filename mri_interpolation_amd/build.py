@@ -17,7 +17,7 @@ CSRC = os.path.join(PKG, "csrc")
 OBJ = os.path.join(PKG, "build")
 LIB = os.path.join(PKG, "libmri_inr.so")
 SOURCES = ["hashgrid.hip", "hashgrid_bwd.hip", "linear.hip", "linear_small.hip", "mlp_fused.hip", "mlp_x3.hip", "train_ops.hip",
-           "frequency.hip", "siren_chain.hip", "siren_rows.hip", "fused_step.hip", "psf.hip"]
+           "frequency.hip", "siren_chain.hip", "siren_rows.hip", "fused_step.hip", "psf.hip", "batchnorm.hip"]
 FLAGS = ["-O3", "--offload-arch=gfx950", "-std=c++17", "-fPIC",
          # the reference multiplies and adds separately (encoding.py:111-128, torch Adam);
          # keep those roundings instead of contracting to fma
@@ -54,7 +54,7 @@ def build(force: bool = False, verbose: bool = False) -> str:
     """Compile every HIP source for gfx950 and link libmri_inr.so; returns its path."""
     os.makedirs(OBJ, exist_ok=True)
     headers = [os.path.join(CSRC, h) for h in ("common.h", "hashgrid_common.h", "device_math.h", "bf16x3.h",
-                                               "mlp_fused.h")] + [os.path.join(ROOT, "include", "mri_inr.h")]
+                                               "mlp_fused.h", "siren_chain.h")] + [os.path.join(ROOT, "include", "mri_inr.h")]
     objs, procs = [], []
     for src in SOURCES:
         s = os.path.join(CSRC, src)

@@ -811,6 +811,121 @@ def psf_conv(z, w):
     return PsfConvFunction.apply(z, w)
 
 
+# --------------------------------------------------------------------------- BatchNorm1d + activation
+_BN_ACTIVATIONS = (ACT_IDENTITY, ACT_RELU, ACT_GELU)
+
+
+def bn_workspace_bytes(n: int, C: int) -> int:
+    need = _lib.load().mri_bn_workspace_bytes(int(n), int(C))
+    if need < 0:
+        raise ValueError(f"BatchNorm kernels: n = {n}, C = {C} is not a supported shape (1 <= C <= 1024)")
+    return need
+
+
+def bn_workspace(n: int, C: int, device) -> torch.Tensor:
+    """Scratch of bn_stats / bn_act_backward for a batch of n rows and C features (float64 chunk sums)."""
+    return torch.empty((bn_workspace_bytes(n, C) + 7) // 8, dtype=torch.float64, device=device)
+
+
+def _bn_matrix(t, C, what):
+    if t.dim() != 2 or t.shape[1] != C or t.stride(1) != 1 or (t.shape[0] > 1 and t.stride(0) < C):
+        raise ValueError(f"{what} {tuple(t.shape)} (strides {tuple(t.stride())}): expected (n, {C}) with unit "
+                         "column stride")
+
+
+def _bn_vectors(C, **vectors):
+    for name, t in vectors.items():
+        if t is not None and (t.numel() != C or not t.is_contiguous()):
+            raise ValueError(f"{name} {tuple(t.shape)}: expected {C} contiguous values")
+
+
+def _bn_workspace_arg(ws, n, C, device):
+    if ws is None:
+        return bn_workspace(n, C, device)
+    if ws.numel() * ws.element_size() < bn_workspace_bytes(n, C):
+        raise ValueError(f"BatchNorm workspace of {ws.numel() * ws.element_size()} bytes, "
+                         f"{bn_workspace_bytes(n, C)} needed")
+    return ws
+
+
+def bn_stats(z, running_mean=None, running_var=None, num_batches_tracked=None, momentum: float = 0.1,
+             eps: float = 1e-5, save=None, ws=None):
+    """Batch statistics of z (n, C) and nn.BatchNorm1d's train() update of its buffers, in place
+    (mri_bn_stats).  Returns save (2, C): batch mean and 1 / sqrt(biased var + eps)."""
+    _gpu(z, running_mean, running_var, save)
+    n, C = z.shape[0], z.shape[-1]
+    _bn_matrix(z, C, "z")
+    if n < 2:
+        raise ValueError(f"Expected more than 1 value per channel when training, got input size {tuple(z.shape)}")
+    _bn_vectors(C, running_mean=running_mean, running_var=running_var)
+    if num_batches_tracked is not None and (num_batches_tracked.dtype != torch.int64
+                                            or not num_batches_tracked.is_cuda):
+        raise TypeError("num_batches_tracked must be an int64 tensor on the GPU")
+    if save is None:
+        save = torch.empty((2, C), device=z.device, dtype=torch.float32)
+    elif save.numel() != 2 * C or not save.is_contiguous():
+        raise ValueError(f"save {tuple(save.shape)}: expected (2, {C}) contiguous")
+    ws = _bn_workspace_arg(ws, n, C, z.device)
+    _lib.call("mri_bn_stats", _ptr(z), z.stride(0), n, C, float(momentum), float(eps), _ptr(running_mean),
+              _ptr(running_var), _ptr(num_batches_tracked), _ptr(save), _ptr(ws), ws.numel() * ws.element_size(),
+              _stream())
+    return save
+
+
+def bn_act_forward(z, gamma, beta, activation=ACT_IDENTITY, save=None, running_mean=None, running_var=None,
+                   eps: float = 1e-5, out=None):
+    """y = act(gamma (z - mean) invstd + beta) (mri_bn_act_forward).  `save` (from bn_stats): the training
+    form; else the eval form with the running statistics, which are not modified.  `out` may be z."""
+    _gpu(z, gamma, beta, save, running_mean, running_var, out)
+    n, C = z.shape[0], z.shape[-1]
+    _bn_matrix(z, C, "z")
+    if activation not in _BN_ACTIVATIONS:
+        raise ValueError(f"activation code {activation}: identity, ReLU or GELU")
+    if save is None and (running_mean is None or running_var is None):
+        raise ValueError("bn_act_forward needs `save` (training) or running_mean and running_var (eval)")
+    _bn_vectors(C, gamma=gamma, beta=beta, running_mean=running_mean, running_var=running_var)
+    if save is not None and (save.numel() != 2 * C or not save.is_contiguous()):
+        raise ValueError(f"save {tuple(save.shape)}: expected (2, {C}) contiguous")
+    if out is None:
+        out = torch.empty((n, C), device=z.device, dtype=torch.float32)
+    _bn_matrix(out, C, "out")
+    if out.shape[0] != n:
+        raise ValueError(f"out has {out.shape[0]} rows, z {n}")
+    _lib.call("mri_bn_act_forward", _ptr(z), z.stride(0), n, C, _ptr(save),
+              None if save is not None else _ptr(running_mean), None if save is not None else _ptr(running_var),
+              float(eps), _ptr(gamma), _ptr(beta), activation, _ptr(out), out.stride(0), _stream())
+    return out
+
+
+def bn_act_backward(dy, z, save, gamma, beta, d_gamma, d_beta, activation=ACT_IDENTITY, dz=None,
+                    overwrite: bool = False, ws=None):
+    """Backward of bn_act_forward's training form (mri_bn_act_backward): returns dz (default: in place of
+    dy); d_gamma / d_beta are added to, or written with `overwrite`."""
+    _gpu(dy, z, save, gamma, beta, d_gamma, d_beta, dz)
+    n, C = z.shape[0], z.shape[-1]
+    _bn_matrix(z, C, "z")
+    _bn_matrix(dy, C, "dy")
+    if dy.shape[0] != n:
+        raise ValueError(f"dy has {dy.shape[0]} rows, z {n}")
+    if n < 2:
+        raise ValueError(f"Expected more than 1 value per channel when training, got input size {tuple(z.shape)}")
+    if activation not in _BN_ACTIVATIONS:
+        raise ValueError(f"activation code {activation}: identity, ReLU or GELU")
+    _bn_vectors(C, gamma=gamma, beta=beta, d_gamma=d_gamma, d_beta=d_beta)
+    if save.numel() != 2 * C or not save.is_contiguous():
+        raise ValueError(f"save {tuple(save.shape)}: expected (2, {C}) contiguous")
+    if dz is None:
+        dz = dy
+    _bn_matrix(dz, C, "dz")
+    if dz.shape[0] != n:
+        raise ValueError(f"dz has {dz.shape[0]} rows, z {n}")
+    ws = _bn_workspace_arg(ws, n, C, z.device)
+    _lib.call("mri_bn_act_backward", _ptr(dy), dy.stride(0), _ptr(z), z.stride(0), n, C, _ptr(save), _ptr(gamma),
+              _ptr(beta), activation, _ptr(dz), dz.stride(0), _ptr(d_gamma), _ptr(d_beta), 1 if overwrite else 0,
+              _ptr(ws), ws.numel() * ws.element_size(), _stream())
+    return dz
+
+
 def adam_step(param, grad, exp_avg, exp_avg_sq, lr, beta1, beta2, eps, step,
               grad_scale: float = 1.0):
     _gpu(param, grad, exp_avg, exp_avg_sq)

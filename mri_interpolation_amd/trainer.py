@@ -11,7 +11,11 @@ compiled into an explicit kernel chain, `FusedStep`, with no autograd graph:
 
 All activations live in workspaces allocated once per batch size; the encoder output and its
 gradient use the feature-major layout so the hash kernels store/load coalesced.
-Other models (e.g. the BatchNorm decoder) run `training_step` + autograd, op by op.
+The reference's default HashMLP (Linear -> BatchNorm1d -> GELU blocks) has such a chain too, the
+BatchNorm plan (`FusedStep(..., batch_norm=True)`, `Trainer(fused_batchnorm=True)`): per block
+linear_fwd -> bn_stats -> bn_act_forward, and bn_act_backward in front of the Linear's backward
+(csrc/batchnorm.hip).  It is opt-in; without the flag that model runs `training_step` + autograd,
+op by op, as does every model that is no plain chain (ModulatedSirenNet).
 """
 import contextlib
 import ctypes as C
@@ -26,12 +30,49 @@ from .datamodules import BatchPipeline, DeviceLoader
 
 
 class _Layer:
-    def __init__(self, weight, bias, activation, w0):
+    def __init__(self, weight, bias, activation, w0, bn=None, bn_activation=ops.ACT_IDENTITY):
         self.weight, self.bias, self.activation, self.w0 = weight, bias, activation, w0
+        # BatchNorm plan: the block's nn.BatchNorm1d module (its parameters and buffers are read and
+        # written in place) and the activation behind it; `activation` (the Linear's epilogue) is identity
+        self.bn, self.bn_activation = bn, bn_activation
 
 
-def fusable_layers(model) -> Optional[tuple]:
-    """(encoder or None, [_Layer, ...]) if the model is a plain chain of fused layers."""
+def _batchnorm_layers(model) -> Optional[list]:
+    """The BatchNorm plan of a HashMLP whose blocks are FusedLinear, nn.BatchNorm1d, activation, Dropout(0):
+    [_Layer, ...] carrying the BatchNorm modules; None if no block holds a BatchNorm1d; ValueError (with
+    the reason) for a BatchNorm decoder the kernels do not cover."""
+    blocks = [list(block) for block in model.decoder]
+    if not any(isinstance(m, torch.nn.BatchNorm1d) for block in blocks for m in block):
+        return None
+    layers = []
+    for i, block in enumerate(blocks):
+        if len(block) != 4 or not isinstance(block[0], models.FusedLinear) \
+                or not isinstance(block[1], torch.nn.BatchNorm1d) or not isinstance(block[3], torch.nn.Dropout):
+            raise ValueError(f"fused BatchNorm step: decoder block {i} is not Linear, BatchNorm1d, activation, "
+                             "Dropout")
+        lin, bn, act, drop = block
+        if drop.p != 0.0:
+            raise ValueError(f"fused BatchNorm step: dropout p = {drop.p} in block {i} (only Dropout(0) is fused)")
+        code = models._activation_code(act)
+        if code is None or code[0] not in (ops.ACT_IDENTITY, ops.ACT_RELU, ops.ACT_GELU):
+            raise ValueError(f"fused BatchNorm step: activation {type(act).__name__} in block {i} has no fused "
+                             "code (identity, ReLU or erf-GELU)")
+        if lin.activation_code != ops.ACT_IDENTITY:
+            raise ValueError(f"fused BatchNorm step: the Linear of block {i} carries an activation of its own")
+        if not bn.affine:
+            raise ValueError(f"fused BatchNorm step: BatchNorm1d(affine=False) in block {i}")
+        if not bn.track_running_stats or bn.running_mean is None:
+            raise ValueError(f"fused BatchNorm step: BatchNorm1d(track_running_stats=False) in block {i}")
+        if bn.momentum is None:
+            raise ValueError(f"fused BatchNorm step: BatchNorm1d(momentum=None) (cumulative average) in block {i}")
+        layers.append(_Layer(lin.weight, lin.bias, ops.ACT_IDENTITY, 1.0, bn=bn, bn_activation=code[0]))
+    return layers
+
+
+def fusable_layers(model, batch_norm: bool = False) -> Optional[tuple]:
+    """(encoder or None, [_Layer, ...]) if the model is a plain chain of fused layers.  `batch_norm`: also
+    accept the reference's BatchNorm decoder blocks of HashMLP (the BatchNorm plan; a BatchNorm decoder the
+    kernels do not cover raises ValueError with the reason)."""
     enc, layers = None, []
     if isinstance(model, models.ModulatedSirenNet):
         return None  # two interleaved stacks: runs training_step + autograd over the HIP ops
@@ -43,6 +84,10 @@ def fusable_layers(model) -> Optional[tuple]:
         return enc, layers
     if isinstance(model, models.HashMLP):
         enc = model.encoder
+        if batch_norm:
+            bn_layers = _batchnorm_layers(model)
+            if bn_layers is not None:
+                return enc, bn_layers
         for block in model.decoder:
             lin, norm, act, drop = block[0], block[1], block[2], block[3]
             if not isinstance(norm, models._Fused):
@@ -67,10 +112,17 @@ def fusable_layers(model) -> Optional[tuple]:
 class FusedStep:
     """Explicit forward / backward kernel chain over preallocated workspaces."""
 
-    def __init__(self, model, optimizer: optim.Adam, world: int = 1, psf_row_budget: int = 1 << 20):
-        plan = fusable_layers(model)
+    def __init__(self, model, optimizer: optim.Adam, world: int = 1, psf_row_budget: int = 1 << 20,
+                 batch_norm: bool = False):
+        plan = fusable_layers(model, batch_norm=batch_norm)
         if plan is None:
             raise ValueError("model is not a fusable chain")
+        # BatchNorm plan (csrc/batchnorm.hip): per block linear_fwd -> bn_stats -> bn_act_forward, and
+        # bn_act_backward in front of the Linear's backward kernels
+        self.bn = any(l.bn is not None for l in plan[1])
+        if self.bn and world > 1:
+            raise ValueError("fused BatchNorm step: batch statistics are not shard-invariant, several ranks "
+                             f"(world = {world}) would need SyncBatchNorm; train on one device")
         # PsfSirenNet: the chain's training step runs on the n S expanded rows, and the loss is taken
         # through the PSF (_psf_pass); at most psf_row_budget expanded rows are in flight at once
         self.psf_row_budget = int(psf_row_budget)
@@ -87,6 +139,8 @@ class FusedStep:
         self._grads = [(self.flat.grad_view(l.weight),
                         self.flat.grad_view(l.bias) if l.bias is not None else None)
                        for l in self.layers]
+        self._bn_grads = [(self.flat.grad_view(l.bn.weight), self.flat.grad_view(l.bn.bias))
+                          if l.bn is not None else None for l in self.layers]
         self._table_grad = self.flat.grad_view(self.encoder.table) if self.encoder else None
         self.tiny = self._tiny_mlp_plan()
         self.use_tiny = self.tiny is not None
@@ -185,7 +239,7 @@ class FusedStep:
         """Parameters for the single-kernel tiny MLP (csrc/mlp_fused.hip) if the decoder is
         in -> H -> H -> 1 with ReLU hidden layers, a linear output and biases everywhere."""
         ls = self.layers
-        if self.encoder is None or len(ls) != 3 or any(l.bias is None for l in ls):
+        if self.bn or self.encoder is None or len(ls) != 3 or any(l.bias is None for l in ls):
             return None
         if [l.activation for l in ls] != [ops.ACT_RELU, ops.ACT_RELU, ops.ACT_IDENTITY]:
             return None
@@ -200,7 +254,7 @@ class FusedStep:
         """Arguments of the fused SIREN chain kernels (csrc/siren_chain.hip) if the model is
         dim_in -> 256 x n (sine) -> 1 (linear head) with biases everywhere."""
         ls = self.layers
-        if self.encoder is not None or len(ls) < 2 or any(l.bias is None for l in ls):
+        if self.bn or self.encoder is not None or len(ls) < 2 or any(l.bias is None for l in ls):
             return None
         if any(l.activation != ops.ACT_SINE for l in ls[:-1]) or ls[-1].activation != ops.ACT_IDENTITY:
             return None
@@ -299,12 +353,20 @@ class FusedStep:
                 ws["dz"] = [new(n, l.weight.shape[0]) for l in self.layers]
                 if self.encoder is not None:
                     ws["d_enc"] = new(self.encoder.output_dim, n)
+            if self.bn and train:
+                # z: the Linear outputs (all the BatchNorm backward keeps); save: batch mean and invstd
+                ws["z"] = [new(n, l.weight.shape[0]) for l in self.layers]
+                ws["bn_save"] = [new(2, l.weight.shape[0]) for l in self.layers]
+                ws["bn_ws"] = ops.bn_workspace(n, max(l.weight.shape[0] for l in self.layers), dev)
             self._ws = {k: v for k, v in self._ws.items() if k[1] != train}  # keep one size
             self._ws[key] = ws
         return ws
 
     def forward(self, coords: torch.Tensor, train: bool = False):
         n = coords.shape[0]
+        if self.bn and train and n < 2:
+            raise ValueError(f"Expected more than 1 value per channel when training, got a batch of {n} row "
+                             "(BatchNorm needs batch statistics)")
         ws = self._workspace(n, train)
         x, feature_major = coords, False
         self._overlapped = False
@@ -343,6 +405,8 @@ class FusedStep:
                                   act=ws["y"][:n_sine] if train else None,
                                   deriv=ws["deriv"][:n_sine] if train else None, y=ws["y"][-1])
             return ws["y"][-1], ws
+        if self.bn:
+            return self._bn_forward(x, feature_major, ws, train), ws
         with self._phase("mlp_fwd"):
             for i, l in enumerate(self.layers):
                 deriv = ws["deriv"][i] if train else None
@@ -352,6 +416,31 @@ class FusedStep:
                                        x_feature_major=feature_major)
                 feature_major = False
         return x, ws
+
+    def _bn_forward(self, x, feature_major, ws, train):
+        """The BatchNorm plan's decoder.  Training: z_i = Linear(x) is kept, the batch statistics go to the
+        save area and the module's running buffers are updated in place (once per call, as the module's
+        forward does).  Inference: the eval form with the running statistics, in place on the Linear output."""
+        for i, l in enumerate(self.layers):
+            bn = l.bn
+            with self._phase("mlp_fwd"):
+                z = ops.linear_forward(x, l.weight.data, None if l.bias is None else l.bias.data,
+                                       ops.ACT_IDENTITY, 1.0, out=ws["z"][i] if train else ws["y"][i],
+                                       x_feature_major=feature_major)
+            feature_major = False
+            if train:
+                with self._phase("bn_stats"):
+                    ops.bn_stats(z, bn.running_mean, bn.running_var, bn.num_batches_tracked, bn.momentum, bn.eps,
+                                 save=ws["bn_save"][i], ws=ws["bn_ws"])
+                with self._phase("bn_fwd"):
+                    x = ops.bn_act_forward(z, bn.weight.data, bn.bias.data, l.bn_activation,
+                                           save=ws["bn_save"][i], out=ws["y"][i])
+            else:
+                with self._phase("bn_fwd"):
+                    x = ops.bn_act_forward(z, bn.weight.data, bn.bias.data, l.bn_activation,
+                                           running_mean=bn.running_mean, running_var=bn.running_var, eps=bn.eps,
+                                           out=z)
+        return x
 
     def _hash_workspace(self, n: int):
         """Scratch of the table-gradient kernels, owned by this FusedStep (two models in one
@@ -605,6 +694,11 @@ class FusedStep:
                 gw, gb = self._grads[i]
                 first_on_encoder = i == 0 and self.encoder is not None
                 x = ws["enc"] if first_on_encoder else (coords if i == 0 else ws["y"][i - 1])
+                if l.bn is not None:  # dz: dL/dy of this block -> dL/dz, in place
+                    with self._phase("bn_bwd"):
+                        ops.bn_act_backward(dz, ws["z"][i], ws["bn_save"][i], l.bn.weight.data, l.bn.bias.data,
+                                            self._bn_grads[i][0], self._bn_grads[i][1], l.bn_activation,
+                                            ws=ws["bn_ws"])
                 ops.linear_backward_weight(dz, x, gw, gb, x_feature_major=first_on_encoder)
                 if i > 0:
                     mode, g = self._deriv_of(i - 1, ws)
@@ -653,6 +747,9 @@ class FusedStep:
         `late_work()` (e.g. BatchPipeline.produce_late: the production of a whole GROUP of later batches)
         is queued on the same stream behind that count, so that nothing the next step waits for sits
         behind it."""
+        if self.bn and coords.shape[0] < 2:  # what nn.BatchNorm1d raises in train(), before anything is queued
+            raise ValueError("Expected more than 1 value per channel when training, got a batch of "
+                             f"{coords.shape[0]} row (BatchNorm needs batch statistics)")
         if self._batch_event is not None:  # this batch was produced on the side stream during the last step
             torch.cuda.current_stream().wait_event(self._batch_event)
             self._batch_event = None
@@ -804,6 +901,8 @@ class SteadyLoop:
         ld = pipe.loader
         if step.psf is not None:
             return "PsfSirenNet: the PSF step runs eagerly (FusedStep.train_step), it has no native form"
+        if step.bn:
+            return "the BatchNorm plan runs eagerly (FusedStep.train_step), it has no native form"
         if step.world != 1 and (step.dp_mode != "all_reduce" or step.grad_buckets > 1):
             return "several ranks: the plain all-reduce form only (one reduction of the flat gradient)"
         if not (step.use_tiny and step.encoder is not None):
@@ -1045,8 +1144,11 @@ class Trainer:
     def __init__(self, max_epochs: int = 1, max_steps: int = -1, accelerator: str = "gpu",
                  precision: int = 32, log_every: int = 0, distributed: bool = True,
                  accumulate_grad_batches=None, dp_mode: str = "all_reduce", grad_buckets: int = 1,
-                 batch_group: int = 1, native_steps: bool = True):
-        """`accumulate_grad_batches`: an int k (gradients of k consecutive batches are summed,
+                 batch_group: int = 1, native_steps: bool = True, fused_batchnorm: bool = False):
+        """`fused_batchnorm`: train (and predict) the reference's BatchNorm decoder of HashMLP through
+        FusedStep's BatchNorm plan instead of training_step + autograd (opt-in; on this path `predict`
+        does not collect `model.latents`, as on the other fused paths).
+        `accumulate_grad_batches`: an int k (gradients of k consecutive batches are summed,
         each scaled by 1/k, before one Adam step -- what `pl.Trainer(accumulate_grad_batches=k)`
         does, reference launcher.py:159-161) or a mapping {epoch: k} (k from that epoch on, the
         scheduler form the reference's config holds, config/base.py:27).  Like Lightning, an
@@ -1063,6 +1165,7 @@ class Trainer:
         self.grad_buckets = int(grad_buckets)  # level groups of the table gradient's reduction, see there
         self.batch_group = int(batch_group)    # batches per launch of the on-device producer (BatchPipeline)
         self.native_steps = bool(native_steps)  # queue steady-state steps with one library call (SteadyLoop)
+        self.fused_batchnorm = bool(fused_batchnorm)  # FusedStep's BatchNorm plan for the default HashMLP
         self.rank, self.world = 0, 1
         if distributed:
             rank, world, _ = parallel.env_world()
@@ -1086,7 +1189,7 @@ class Trainer:
             opt = model.configure_optimizers()
             model.optimizer = opt
         try:
-            self.fused = FusedStep(model, opt, self.world)
+            self.fused = FusedStep(model, opt, self.world, batch_norm=self.fused_batchnorm)
         except ValueError:
             self.fused = None
             opt.flatten()
@@ -1203,7 +1306,7 @@ class Trainer:
         if fused is None:
             try:
                 fused = FusedStep(model, model.optimizer if hasattr(model, "optimizer")
-                                  else model.configure_optimizers(), 1)
+                                  else model.configure_optimizers(), 1, batch_norm=self.fused_batchnorm)
             except ValueError:
                 fused = None
         out = []
