@@ -321,6 +321,38 @@ int mri_hash_tiny_mlp_train(const mri_grid_desc* grid, const float* table, const
                             int64_t d_enc_ld, float* loss_out, float* y, int32_t overwrite,
                             void* workspace, int64_t workspace_bytes, void* stream);
 
+/* ---- fused shallow decoder -------------------------------------------------------------------
+ * The decoder of the notebook's HashMLP without BatchNorm (reference models.py:712-739 minus the
+ * BatchNorm1d, notebook cell 37): k_in -> hidden -> 1 with an activation after EACH of the two Linears,
+ *   y = act_out(act_hidden(x W1^T + b1) . w2 + b2),
+ * in ONE persistent kernel per call: nothing (n, hidden)-sized goes to memory (csrc/mlp_shallow.hip; the
+ * three matrix products are f32 MFMAs).
+ *   1 <= k_in <= 32, hidden in {32, 64, 128}, dim_out 1, biases on both layers; act_hidden and act_out
+ *   each one of MRI_ACT_IDENTITY / MRI_ACT_RELU / MRI_ACT_GELU (mri_shallow_mlp_supported: 1 or 0).
+ *   x (k_in, n) FEATURE-MAJOR (the layout mri_hashgrid_forward writes), w1 (hidden, k_in), w2 (1, hidden)
+ *   row-major as nn.Linear stores them, y (n).
+ * mri_shallow_mlp_train: forward + F.mse_loss(target, y) + backward in one pass over a slice of n rows of a
+ *   batch of n_total (n <= n_total; the mean of the loss and the gradient scale are taken over n_total, so
+ *   the slices of a batch add up to the whole batch): gradients of mean((y - target)^2) / grad_divisor.
+ *   overwrite = 0: d_w1, d_b1, d_w2, d_b2 and loss_out[0] are ADDED to, 1: overwritten.  d_x (k_in, n)
+ *   feature-major = dLoss / dx is written (optional, may be NULL), y (optional) receives the predictions.
+ *   Per-workgroup partial sums go through `workspace` (mri_shallow_mlp_workspace_bytes, -1 for an
+ *   unsupported shape; no initialisation needed) and are added in a fixed order: bitwise reproducible.
+ * n = 0 is a no-op; NULL buffers, an unsupported shape or a short workspace return
+ * MRI_ERR_INVALID_ARGUMENT before anything is queued. */
+int mri_shallow_mlp_supported(int32_t k_in, int32_t hidden, int32_t dim_out, int32_t act_hidden,
+                              int32_t act_out);
+int64_t mri_shallow_mlp_workspace_bytes(int32_t k_in, int32_t hidden, int64_t n);
+int mri_shallow_mlp_forward(const float* x, int64_t n, int32_t k_in, int32_t hidden, const float* w1,
+                            const float* b1, const float* w2, const float* b2, int32_t act_hidden,
+                            int32_t act_out, float* y, void* stream);
+int mri_shallow_mlp_train(const float* x, const float* target, int64_t n, int64_t n_total, int32_t k_in,
+                          int32_t hidden, const float* w1, const float* b1, const float* w2,
+                          const float* b2, int32_t act_hidden, int32_t act_out, float grad_divisor,
+                          float* d_w1, float* d_b1, float* d_w2, float* d_b2, float* d_x /* may be NULL */,
+                          float* loss_out, float* y /* may be NULL */, int32_t overwrite, void* workspace,
+                          int64_t workspace_bytes, void* stream);
+
 /* Gradient w.r.t. the COORDINATES: the reference detaches only the integer part of x * res
  * (encoding.py:111-113), so autograd carries d out / d x through the interpolation weights:
  * d_x[i][d] = res_d * sum over levels and corners of (+-1) prod_{e != d} w_e * <d_out, row>.

@@ -53,6 +53,9 @@ def parse_args(argv=None):
                    help="HashMLP with the reference's BatchNorm decoder (the default model): train and predict "
                         "through the fused BatchNorm kernel chain instead of training_step + autograd; on this "
                         "path predict does not collect model.latents (as on the other fused paths)")
+    p.add_argument("--no_batchnorm", action="store_true",
+                   help="HashMLP without the BatchNorm1d of its decoder blocks, GELU kept (the notebook's decoder, "
+                        "Linear -> GELU twice): trains through the one-kernel shallow decoder step")
     p.add_argument("--holdout_odd_frames", action="store_true",
                    help="train on the even frames of the last axis, report PSNR on the odd ones "
                         "(BASELINE config 5 protocol)")
@@ -83,6 +86,14 @@ def psf_spacing(shape, k, norm_siren=True):
     one voxel gets 0."""
     lo = -1.0 if norm_siren else 0.0
     return tuple((1.0 - lo) / (s - 1) / 2 if s > 1 else 0.0 for s in list(shape)[:k])
+
+
+def apply_decoder_flags(config, args):
+    """--no_batchnorm on a HashMLP config: the decoder blocks lose their BatchNorm1d and keep their activation
+    (GELU by default).  --tiny_mlp keeps its meaning (it sets a ReLU decoder without BatchNorm itself)."""
+    if getattr(args, "no_batchnorm", False) and config.model_class == "HashMLP":
+        config.batch_norm = False
+    return config
 
 
 def build_model(config, models):
@@ -141,7 +152,7 @@ def main(argv=None):
     if os.path.exists(enco_path):
         config.enco_config = cfg.load_json(enco_path)  # reference launcher.py:73-74
     overrides = {k: v for k, v in vars(args).items()
-                 if k not in ("synthetic", "tiny_mlp", "out_dir", "max_steps", "log_every",
+                 if k not in ("synthetic", "tiny_mlp", "no_batchnorm", "out_dir", "max_steps", "log_every",
                               "resume_optimizer", "restore_lr", "unsafe_checkpoint", "accelerator",
                               "enco_config_path", "holdout_odd_frames", "base_resolution",
                               "finest_resolution")}
@@ -165,6 +176,7 @@ def main(argv=None):
         config.dim_hidden = args.dim_hidden or int(net.get("n_neurons", 128))
         config.n_layers = args.n_layers or int(net.get("n_hidden_layers", 2)) + 1
         config.activation, config.batch_norm, config.final_activation_on = "ReLU", False, False
+    apply_decoder_flags(config, args)
     for name in ("base_resolution", "finest_resolution"):  # explicit grids win over the JSON's
         if wants_hash and getattr(args, name):
             setattr(config, name, cfg.parse_resolution(getattr(args, name)))

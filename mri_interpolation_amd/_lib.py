@@ -116,6 +116,9 @@ SIGNATURES = {
     "mri_bn_act_forward": [_P, _I64, _I64, _I32, _P, _P, _P, _D, _P, _P, _I32, _P, _I64, _P],
     "mri_bn_act_backward": [_P, _I64, _P, _I64, _I64, _I32, _P, _P, _P, _I32, _P, _I64, _P, _P, _I32, _P, _I64,
                             _P],
+    "mri_shallow_mlp_forward": [_P, _I64, _I32, _I32, _P, _P, _P, _P, _I32, _I32, _P, _P],
+    "mri_shallow_mlp_train": [_P, _P, _I64, _I64, _I32, _I32, _P, _P, _P, _P, _I32, _I32, _F, _P, _P, _P, _P, _P,
+                              _P, _P, _I32, _P, _I64, _P],
     "mri_adam_step": [_P, _P, _P, _P, _I64, _D, _D, _D, _D, _I32, _F, _P],
     "mri_sample_indices": [C.c_uint64, _I64, _I64, _I64, _I64, _P, _P],
     "mri_fused_step": [_P],
@@ -125,12 +128,14 @@ STRING_GETTERS = ["mri_version", "mri_last_error"]
 INT64_GETTERS = {"mri_hashgrid_backward_workspace_bytes": [C.POINTER(GridDesc), _I64],
                  "mri_fused_step_args_bytes": [],
                  "mri_tiny_mlp_workspace_bytes": [_I32, _I32, _I64],
+                 "mri_shallow_mlp_workspace_bytes": [_I32, _I32, _I64],
                  "mri_bn_workspace_bytes": [_I64, _I32],
                  "mri_siren_backward_workspace_bytes": [_I64, _I32, _I32],
                  "mri_siren_forward_workspace_bytes": [_I32, _I32],
                  "mri_hashgrid_forward_signal_blocks": [C.POINTER(GridDesc), _I64],
                  "mri_tiny_mlp_round_rows": [_I32, _I32, _I64]}
 INT_GETTERS = {"mri_tiny_mlp_supported": [_I32, _I32, _I32],
+               "mri_shallow_mlp_supported": [_I32, _I32, _I32, _I32, _I32],
                "mri_hash_tiny_mlp_supported": [C.POINTER(GridDesc), _I32],
                "mri_tiny_mlp_dx_absmax_supported": [_I32, _I32],
                "mri_siren_supported": [_I32, _I32, _I32, _I32]}  # return a plain value, not a status

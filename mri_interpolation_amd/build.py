@@ -16,7 +16,7 @@ ROOT = os.path.dirname(PKG)
 CSRC = os.path.join(PKG, "csrc")
 OBJ = os.path.join(PKG, "build")
 LIB = os.path.join(PKG, "libmri_inr.so")
-SOURCES = ["hashgrid.hip", "hashgrid_bwd.hip", "linear.hip", "linear_small.hip", "mlp_fused.hip", "mlp_x3.hip", "train_ops.hip",
+SOURCES = ["hashgrid.hip", "hashgrid_bwd.hip", "linear.hip", "linear_small.hip", "mlp_fused.hip", "mlp_x3.hip", "mlp_shallow.hip", "train_ops.hip",
            "frequency.hip", "siren_chain.hip", "siren_rows.hip", "fused_step.hip", "psf.hip", "batchnorm.hip"]
 FLAGS = ["-O3", "--offload-arch=gfx950", "-std=c++17", "-fPIC",
          # the reference multiplies and adds separately (encoding.py:111-128, torch Adam);

@@ -533,6 +533,68 @@ def tiny_mlp_train_slice(x_fm, target, col_offset: int, n: int, params, grads, l
     return loss_out
 
 
+# --------------------------------------------------------------------------- fused shallow decoder
+SHALLOW_ACTIVATIONS = (ACT_IDENTITY, ACT_RELU, ACT_GELU)
+
+
+def shallow_mlp_supported(k_in: int, hidden: int, dim_out: int, act_hidden: int, act_out: int) -> bool:
+    """Is there a one-kernel form of k_in -> hidden -> dim_out with these two activation codes?"""
+    return bool(_lib.load().mri_shallow_mlp_supported(int(k_in), int(hidden), int(dim_out), int(act_hidden),
+                                                      int(act_out)))
+
+
+_shallow_workspace_cache = {}
+
+
+def _shallow_workspace(k_in, hidden, n, device):
+    need = _lib.load().mri_shallow_mlp_workspace_bytes(k_in, hidden, n)
+    if need < 0:
+        raise ValueError(f"shallow decoder {k_in} -> {hidden} -> 1 is not supported")
+    ws = _shallow_workspace_cache.get(device.index)
+    if ws is None or ws.numel() * 4 < need:
+        if ws is not None:  # may still be in use on another stream: see backward_workspace()
+            torch.cuda.synchronize(device)
+        ws = torch.empty((need + 3) // 4, dtype=torch.float32, device=device)
+        _shallow_workspace_cache[device.index] = ws
+    return ws
+
+
+def shallow_mlp_forward(x_fm, params, activations, y=None):
+    """y (n, 1) = act_out(act_hidden(x W1^T + b1) w2^T + b2) for feature-major x (k_in, n);
+    params = [(w1, b1), (w2, b2)], activations = (act_hidden, act_out)."""
+    (w1, b1), (w2, b2) = params
+    _gpu(x_fm, w1, b1, w2, b2, y)
+    k_in, n = x_fm.shape
+    if y is None:
+        y = torch.empty((n, 1), device=x_fm.device, dtype=torch.float32)
+    _lib.call("mri_shallow_mlp_forward", _ptr(x_fm), n, k_in, w1.shape[0], _ptr(w1), _ptr(b1), _ptr(w2),
+              _ptr(b2), int(activations[0]), int(activations[1]), _ptr(y), _stream())
+    return y
+
+
+def shallow_mlp_train(x_fm, target, params, activations, grads, loss_out, d_x=None, y=None,
+                      grad_divisor: float = 1.0, overwrite: bool = False, n_total: Optional[int] = None, ws=None):
+    """Forward + MSE + backward of the shallow decoder in one kernel; grads and loss_out accumulate (or are
+    overwritten when overwrite=True).  `n_total`: the rows of the whole batch this call is a slice of."""
+    (w1, b1), (w2, b2) = params
+    (g1, gb1), (g2, gb2) = grads
+    _gpu(x_fm, target, w1, b1, w2, b2, g1, gb1, g2, gb2, loss_out, d_x, y)
+    k_in, n = x_fm.shape
+    if not x_fm.is_contiguous() or (d_x is not None and not d_x.is_contiguous()):
+        raise ValueError("shallow_mlp_train: x and d_x are contiguous feature-major (k_in, n) blocks")
+    if target.numel() != n:
+        raise ValueError(f"shallow_mlp_train: {target.numel()} targets for {n} rows")
+    if not target.is_contiguous():
+        target = target.contiguous()
+    if ws is None:
+        ws = _shallow_workspace(k_in, w1.shape[0], n, x_fm.device)
+    _lib.call("mri_shallow_mlp_train", _ptr(x_fm), _ptr(target), n, n if n_total is None else int(n_total), k_in,
+              w1.shape[0], _ptr(w1), _ptr(b1), _ptr(w2), _ptr(b2), int(activations[0]), int(activations[1]),
+              float(grad_divisor), _ptr(g1), _ptr(gb1), _ptr(g2), _ptr(gb2), _ptr(d_x), _ptr(loss_out), _ptr(y),
+              1 if overwrite else 0, _ptr(ws), ws.numel() * 4, _stream())
+    return loss_out
+
+
 # ----------------------------------------------------------- lookup and decoder side by side
 def tiny_mlp_round_rows(k_in: int, hidden: int, n: int) -> int:
     """Rows one round of the decoder kernel's workgroups reads (0: no overlapped form)."""

@@ -16,6 +16,9 @@ BatchNorm plan (`FusedStep(..., batch_norm=True)`, `Trainer(fused_batchnorm=True
 linear_fwd -> bn_stats -> bn_act_forward, and bn_act_backward in front of the Linear's backward
 (csrc/batchnorm.hip).  It is opt-in; without the flag that model runs `training_step` + autograd,
 op by op, as does every model that is no plain chain (ModulatedSirenNet).
+The notebook's HashMLP (two blocks Linear -> GELU, no BatchNorm) takes the shallow plan: `train_step` runs its
+decoder -- forward, loss and backward -- as ONE kernel (csrc/mlp_shallow.hip), `forward(train=True)` + `backward()`
+keep the layer kernels.
 """
 import contextlib
 import ctypes as C
@@ -109,6 +112,25 @@ def fusable_layers(model, batch_norm: bool = False) -> Optional[tuple]:
     return None
 
 
+def shallow_plan_matches(has_encoder: bool, batch_norm: bool, shapes, has_bias, activations,
+                         supported=None) -> bool:
+    """Does a decoder take the one-kernel shallow step (csrc/mlp_shallow.hip)?  A pure function of the layer
+    shapes [(out, in), ...], the bias flags and the activation codes: an encoder in front, no BatchNorm plan,
+    exactly two Linears with biases, (H, k_in) then (1, H), both activations among identity / ReLU / GELU,
+    and a kernel for that shape (`supported`, default ops.shallow_mlp_supported)."""
+    if not has_encoder or batch_norm or len(shapes) != 2 or len(has_bias) != 2 or len(activations) != 2:
+        return False
+    if not all(has_bias):
+        return False
+    (h, k_in), second = tuple(shapes[0]), tuple(shapes[1])
+    if second != (1, h):
+        return False
+    if any(a not in ops.SHALLOW_ACTIVATIONS for a in activations):
+        return False
+    supported = ops.shallow_mlp_supported if supported is None else supported
+    return bool(supported(k_in, h, 1, activations[0], activations[1]))
+
+
 class FusedStep:
     """Explicit forward / backward kernel chain over preallocated workspaces."""
 
@@ -144,6 +166,11 @@ class FusedStep:
         self._table_grad = self.flat.grad_view(self.encoder.table) if self.encoder else None
         self.tiny = self._tiny_mlp_plan()
         self.use_tiny = self.tiny is not None
+        # k_in -> H -> 1 with an activation behind each Linear (the notebook's GELU decoder): train_step and
+        # forward(train=False) run ONE decoder kernel; forward(train=True) + backward() keep the layer
+        # kernels.  use_shallow = False: the layer kernels everywhere
+        self.shallow = self._shallow_plan()
+        self.use_shallow = self.shallow is not None
         self.chain = self._siren_chain_plan()
         self.use_chain = self.chain is not None
         self.psf = self._psf_plan(model)
@@ -249,6 +276,38 @@ class FusedStep:
         if not ops.tiny_mlp_supported(k_in, h, 1):
             return None
         return dict(params=[(l.weight.data, l.bias.data) for l in ls], grads=self._grads)
+
+    def _shallow_plan(self):
+        """Arguments of the shallow decoder kernels (csrc/mlp_shallow.hip), or None (shallow_plan_matches)."""
+        ls = self.layers
+        if not shallow_plan_matches(self.encoder is not None, self.bn, [tuple(l.weight.shape) for l in ls],
+                                    [l.bias is not None for l in ls], [l.activation for l in ls]):
+            return None
+        return dict(params=[(l.weight.data, l.bias.data) for l in ls],
+                    activations=(ls[0].activation, ls[1].activation), grads=self._grads)
+
+    def _shallow_pass(self, coords, target, first, step, divisor):
+        """lookup -> decoder forward + loss + backward in one kernel -> decoder-gradient reduction -> table
+        gradient: the order of the tiny-MLP branch of backward().  Every gradient and the loss are
+        overwritten (first) or added to by the kernels: no zeroing pass over the flat buffer."""
+        ws = self._workspace(coords.shape[0], True)
+        s = self.shallow
+        with self._phase("hashgrid_fwd"):
+            x = ops.hashgrid_forward(self.encoder.desc, coords, self.encoder.table.data, out=ws["enc"],
+                                     feature_major=True)
+        with self._phase("mlp_fused"):
+            if not first:
+                self.loss.zero_()  # the kernel adds to it: keep it this batch's loss
+            ops.shallow_mlp_train(x, target, s["params"], s["activations"], s["grads"], self.loss,
+                                  d_x=ws["d_enc"], y=ws["y"][-1],
+                                  grad_divisor=float(self.world) * float(divisor), overwrite=first)
+        started = self._reduce_decoder_grads() if step else []
+        with self._phase("hashgrid_bwd"):
+            if first and step and self._hash_backward_adam(coords, ws["d_enc"]):
+                self._pending = []
+            else:
+                self._pending = started + self._hash_backward(coords, ws["d_enc"], overwrite=first,
+                                                              reduce=step)
 
     def _siren_chain_plan(self):
         """Arguments of the fused SIREN chain kernels (csrc/siren_chain.hip) if the model is
@@ -398,6 +457,10 @@ class FusedStep:
                 return ops.tiny_mlp_forward(x, self.tiny["params"], y=ws["y"][-1]), ws
         if self.use_tiny:
             return x, ws  # the training kernel runs forward and backward together
+        if self.use_shallow and self.shallow is not None and not train:
+            with self._phase("mlp_fwd"):
+                return ops.shallow_mlp_forward(x, self.shallow["params"], self.shallow["activations"],
+                                               y=ws["y"][-1]), ws
         if self.use_chain:  # every layer of a row tile in one kernel, activations stay in LDS
             c, n_sine = self.chain, len(self.layers) - 1
             with self._phase("mlp_fwd"):
@@ -813,6 +876,9 @@ class FusedStep:
         elif self.use_chain and self.chain_loss:
             self._pending = []
             self._chain_loss_pass(coords, target, first, divisor)
+        elif self.use_shallow and self.shallow is not None:
+            self._pending = []
+            self._shallow_pass(coords, target, first, step, divisor)
         else:
             _, ws = self.forward(coords, train=True)
             self._pending = []
