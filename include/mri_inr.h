@@ -448,6 +448,58 @@ int mri_siren_forward_loss(const float* x, const float* target, int64_t n, int64
                            float* d_b_last, float* loss_out, void* workspace,
                            int64_t workspace_bytes, void* stream);
 
+/* ---- fused modulated SIREN chain ---------------------------------------------------------------
+ * ModulatedSirenNet.forward (reference models.py:263-322): per layer l the SIREN layer sin(w_l (a_{l-1} Ws_l^T +
+ * bs_l)) (SirenLayer.forward, models.py:153-156; w_0 = w0_first) multiplied elementwise by the modulator's hidden
+ * state h_l = relu([h_{l-1}, z] Wm_l^T + bm_l) (Modulator.forward, models.py:236-260; z = x, layer 0 sees z only),
+ * then the linear head -- in ONE persistent kernel (csrc/modsiren.hip): both states of a row tile stay in LDS across
+ * all layers, the hidden x hidden weights of both stacks stream from L2.
+ * Supported (mri_modsiren_supported is the truth): 1 <= dim_in <= 8, hidden in {64, 128},
+ * 2 <= n_layers <= MRI_SIREN_MAX_LAYERS, dim_out = 1, biases everywhere.  An unsupported shape is refused with
+ * MRI_ERR_INVALID_ARGUMENT and its reason in mri_last_error.
+ * siren_weight / siren_bias: HOST arrays of n_layers + 1 device pointers -- [0] (hidden, dim_in), [1 .. n-1]
+ * (hidden, hidden), [n] the head (1, hidden).  mod_weight / mod_bias: HOST arrays of n_layers device pointers --
+ * [0] (hidden, dim_in), [l] (hidden, hidden + dim_in), the hidden columns first (the reference concatenates
+ * (hidden, z)).  All row-major and contiguous.
+ * act / hid / dcos / sn: HOST arrays of n_layers device pointers to (n, hidden) row-major, 16-byte aligned buffers
+ * that receive, per layer, a_l = s_l h_l, h_l, h_l w_l cos(.) and s_l = sin(.) for the backward pass -- or all four
+ * NULL (inference: nothing but y is written).  y: (n) predictions.
+ * workspace: mri_modsiren_forward_workspace_bytes device bytes, 16-byte aligned: each call first splits the hidden x
+ * hidden blocks of both stacks there into the three bf16 terms the matrix pipe multiplies (f32-accurate,
+ * csrc/bf16x3.h). */
+int mri_modsiren_supported(int32_t dim_in, int32_t hidden, int32_t n_layers, int32_t dim_out);
+int64_t mri_modsiren_forward_workspace_bytes(int32_t hidden, int32_t n_layers);
+int mri_modsiren_forward(const float* x, int64_t n, int32_t dim_in, int32_t hidden, int32_t n_layers,
+                         const float* const* siren_weight, const float* const* siren_bias,
+                         const float* const* mod_weight, const float* const* mod_bias, float w0_first, float w0,
+                         float* const* act, float* const* hid, float* const* dcos, float* const* sn, float* y,
+                         void* workspace, int64_t workspace_bytes, void* stream);
+/* Training forward WITH the loss (models.py:61-66 training_step: y_pred = forward(x); F.mse_loss(y, y_pred)): the
+ * same kernel also compares its predictions with `target`: dy (n) = 2 (y - target) / (n_total grad_divisor), and
+ * loss_out[0] += sum (y - target)^2 / n_total (n <= n_total: a slice of a batch), the workgroups' shares added in a
+ * fixed order.  Follow with mri_modsiren_backward(dy).  workspace: mri_modsiren_backward_workspace_bytes. */
+int mri_modsiren_forward_loss(const float* x, const float* target, int64_t n, int64_t n_total, int32_t dim_in,
+                              int32_t hidden, int32_t n_layers, const float* const* siren_weight,
+                              const float* const* siren_bias, const float* const* mod_weight,
+                              const float* const* mod_bias, float w0_first, float w0, float grad_divisor,
+                              float* const* act, float* const* hid, float* const* dcos, float* const* sn, float* y,
+                              float* dy, float* loss_out, void* workspace, int64_t workspace_bytes, void* stream);
+/* Backward of the same network (autograd of models.py:263-322 from dy = dLoss / dy): da and the modulator's dz walk
+ * the layers inside LDS (one persistent kernel) and leave once per layer as dzs / dzm -- HOST arrays of n_layers
+ * device pointers to (n, hidden) 16-byte aligned scratch ([0] unused, may be NULL) --; each hidden x hidden weight
+ * gradient is one persistent kernel (the SIREN chain's).  Bias gradients, the head, the first layers and the dim_in
+ * tail columns of the modulator weights are summed per workgroup; all partial sums meet in `workspace` and are added
+ * in a fixed order: no float atomics, bitwise reproducible.  act / hid / dcos / sn: what the forward call stored.
+ * d_siren_weight / d_siren_bias (n_layers + 1 pointers) and d_mod_weight / d_mod_bias (n_layers): gradients are
+ * ADDED to them.  No gradient with respect to x. */
+int64_t mri_modsiren_backward_workspace_bytes(int64_t n, int32_t hidden, int32_t n_layers);
+int mri_modsiren_backward(const float* x, const float* dy, int64_t n, int32_t dim_in, int32_t hidden,
+                          int32_t n_layers, const float* const* siren_weight, const float* const* mod_weight,
+                          const float* const* act, const float* const* hid, const float* const* dcos,
+                          const float* const* sn, float* const* dzs, float* const* dzm,
+                          float* const* d_siren_weight, float* const* d_siren_bias, float* const* d_mod_weight,
+                          float* const* d_mod_bias, void* workspace, int64_t workspace_bytes, void* stream);
+
 /* ---- PsfSirenNet: the acquisition point-spread function -----------------------------------
  * (reference models.py:397-539.)  A target voxel b is the network averaged over S sample points around it:
  * rows b*S + k of the expanded batch hold x[b] + offsets[k], and the voxel value is sum_k w_k z[b*S + k]

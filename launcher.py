@@ -53,6 +53,9 @@ def parse_args(argv=None):
                    help="HashMLP with the reference's BatchNorm decoder (the default model): train and predict "
                         "through the fused BatchNorm kernel chain instead of training_step + autograd; on this "
                         "path predict does not collect model.latents (as on the other fused paths)")
+    p.add_argument("--fused_modulated", action="store_true",
+                   help="ModulatedSirenNet: train and predict through the fused modulated SIREN kernel chain "
+                        "(both stacks of a row tile on chip) instead of training_step + autograd")
     p.add_argument("--no_batchnorm", action="store_true",
                    help="HashMLP without the BatchNorm1d of its decoder blocks, GELU kept (the notebook's decoder, "
                         "Linear -> GELU twice): trains through the one-kernel shallow decoder step")
@@ -215,7 +218,7 @@ def main(argv=None):
     trainer = Trainer(max_epochs=config.epochs, max_steps=args.max_steps, precision=32,
                       log_every=args.log_every,
                       accumulate_grad_batches=config.accumulate_grad_batches,
-                      fused_batchnorm=args.fused_batchnorm)
+                      fused_batchnorm=args.fused_batchnorm, fused_modulated=args.fused_modulated)
     t0 = time.time()
     trainer.fit(model, train_loader)
     train_seconds = time.time() - t0

@@ -8,6 +8,7 @@ import os
 
 MAX_LEVELS = 32
 MAX_DIM = 7
+MAX_SIREN_LAYERS = 8  # MRI_SIREN_MAX_LAYERS
 
 ACT_IDENTITY, ACT_RELU, ACT_SINE, ACT_GELU = 0, 1, 2, 3
 DERIV_NONE, DERIV_MUL, DERIV_RELU_MASK = 0, 1, 2
@@ -108,6 +109,11 @@ SIGNATURES = {
     "mri_siren_forward_loss": [_P, _P, _I64, _I64, _I32, _I32, _I32, C.POINTER(_P), C.POINTER(_P), _F,
                                _F, _F, C.POINTER(_P), C.POINTER(_P), _P, _P, _P, _P, _P, _P, _P,
                                _I64, _P],
+    "mri_modsiren_forward": [_P, _I64, _I32, _I32, _I32] + [C.POINTER(_P)] * 4 + [_F, _F] + [C.POINTER(_P)] * 4
+                            + [_P, _P, _I64, _P],
+    "mri_modsiren_forward_loss": [_P, _P, _I64, _I64, _I32, _I32, _I32] + [C.POINTER(_P)] * 4 + [_F, _F, _F]
+                                 + [C.POINTER(_P)] * 4 + [_P, _P, _P, _P, _I64, _P],
+    "mri_modsiren_backward": [_P, _P, _I64, _I32, _I32, _I32] + [C.POINTER(_P)] * 12 + [_P, _I64, _P],
     "mri_psf_expand": [_P, _I64, _I32, _P, _I32, _P, _P],
     "mri_psf_reduce": [_P, _I64, _I32, _I32, _P, _P, _P],
     "mri_psf_broadcast": [_P, _I64, _I32, _P, _F, _P, _P],
@@ -132,13 +138,16 @@ INT64_GETTERS = {"mri_hashgrid_backward_workspace_bytes": [C.POINTER(GridDesc), 
                  "mri_bn_workspace_bytes": [_I64, _I32],
                  "mri_siren_backward_workspace_bytes": [_I64, _I32, _I32],
                  "mri_siren_forward_workspace_bytes": [_I32, _I32],
+                 "mri_modsiren_backward_workspace_bytes": [_I64, _I32, _I32],
+                 "mri_modsiren_forward_workspace_bytes": [_I32, _I32],
                  "mri_hashgrid_forward_signal_blocks": [C.POINTER(GridDesc), _I64],
                  "mri_tiny_mlp_round_rows": [_I32, _I32, _I64]}
 INT_GETTERS = {"mri_tiny_mlp_supported": [_I32, _I32, _I32],
                "mri_shallow_mlp_supported": [_I32, _I32, _I32, _I32, _I32],
                "mri_hash_tiny_mlp_supported": [C.POINTER(GridDesc), _I32],
                "mri_tiny_mlp_dx_absmax_supported": [_I32, _I32],
-               "mri_siren_supported": [_I32, _I32, _I32, _I32]}  # return a plain value, not a status
+               "mri_siren_supported": [_I32, _I32, _I32, _I32],
+               "mri_modsiren_supported": [_I32, _I32, _I32, _I32]}  # return a plain value, not a status
 
 _lib = None
 

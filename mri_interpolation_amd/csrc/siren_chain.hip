@@ -46,9 +46,8 @@
 namespace mri {
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
+using namespace chain;  // tile-loop helpers shared with modsiren.hip (siren_chain.h)
 
-constexpr int kThreads = 512;  // 8 waves
 constexpr int kWr = 32;        // batch rows per chunk of the weight-gradient kernel
 
 // Geometry for hidden width H: a wave owns a 32 x CT tile of the (rows x H) layer output, the 8
@@ -80,88 +79,6 @@ struct FwdSmem {
   float tgt[S::rows];               // loss mode: the tile's targets, then dLoss / dy
 };
 
-// row of register r of a 32x32 accumulator: (r & 3) + 8 (r >> 2) + 4 (lane >> 5)
-__device__ __forceinline__ int acc_row(int r, int lh) { return (r & 3) + 8 * (r >> 2) + 4 * lh; }
-
-// acc += A B over a 16-deep step, operands in their three bf16 terms: the six products, smallest first
-__device__ __forceinline__ f32x16 mfma32x3(const x3::u32x4& a, const x3::u32x4& b, f32x16 c) {
-  return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(x3::bf16x8, a),
-                                                 __builtin_bit_cast(x3::bf16x8, b), c, 0, 0, 0);
-}
-__device__ __forceinline__ f32x16 mma6_32(const x3::Frag& a, const x3::Frag& b, f32x16 c) {
-  c = mfma32x3(a.l, b.h, c);
-  c = mfma32x3(a.h, b.l, c);
-  c = mfma32x3(a.m, b.m, c);
-  c = mfma32x3(a.m, b.h, c);
-  c = mfma32x3(a.h, b.m, c);
-  c = mfma32x3(a.h, b.h, c);
-  return c;
-}
-__device__ __forceinline__ x3::Frag split_octets(const float4& lo, const float4& hi) {
-  const float v[8] = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
-  return x3::split8(v);
-}
-
-// Queue the LDS-DMA of chunk kc of one split matrix into `dst`: 16-byte slots, lane = slot.  The
-// slot a lane FETCHES is its LDS slot with the half bit XORed by bit 3 of the row, the involution
-// the fragment reads undo: the 16 lanes of a ds_read_b128 group then touch 16 different slots.
-template <class S>
-__device__ __forceinline__ void issue_chunk(const char* __restrict__ wsplit, int kc, char* dst,
-                                            int wave, int lane) {
-  constexpr int slots = 6 * S::H;  // 3 planes x H rows x 2
-  const char* src = wsplit + (int64_t)kc * S::chunk_bytes;
-#pragma unroll
-  for (int i = 0; i < (slots + kThreads - 1) / kThreads; ++i) {
-    const int base = (wave + 8 * i) * 64;
-    if (slots % kThreads != 0 && base >= slots) break;
-    const int slot = base + lane, n = (slot >> 1) % S::H;
-    __builtin_amdgcn_global_load_lds(
-        (const __attribute__((address_space(1))) void*)(src + 16 * (slot ^ ((n >> 3) & 1))),
-        (__attribute__((address_space(3))) void*)(dst + 16 * base), 16, 0, 0);
-  }
-}
-
-// One 16-deep chunk of acc[t] += img[rows][k] * W[cols_t][k] for the wave's 32 x CT tile.  boff[t]: byte offset of
-// the lane's slot of its column 32 t in a term plane.  The image operand is software-pipelined over the chunks of a
-// layer (round 4): `fa` holds THIS chunk's fragment, already split (the image is complete when a layer starts, only
-// the weights arrive chunk by chunk); the f32 words of the NEXT chunk's fragment (`a_next`: the lane's image row at
-// that chunk's first k, + 4 lh; null for a layer's last chunk) are requested together with this chunk's weight
-// fragments and split while this chunk's MFMAs execute.  Measured neutral against reading and splitting in front of
-// the chunk's own MFMAs (config 3 12.82 against 12.81 ms, same flags, same box; EXPERIMENTS.md corrects the first
-// claim); the weight fragments a chunk ahead as well (a three-deep DMA ring) measured slower.
-template <int NT, int H>
-__device__ __forceinline__ void mma_chunk(f32x16 (&acc)[NT], x3::Frag& fa, const float* __restrict__ a_next,
-                                          const char* __restrict__ wb, const int (&boff)[NT]) {
-  x3::Frag fb[NT];
-#pragma unroll
-  for (int t = 0; t < NT; ++t) {
-    fb[t].h = *reinterpret_cast<const x3::u32x4*>(wb + boff[t]);
-    fb[t].m = *reinterpret_cast<const x3::u32x4*>(wb + H * 32 + boff[t]);
-    fb[t].l = *reinterpret_cast<const x3::u32x4*>(wb + 2 * H * 32 + boff[t]);
-  }
-  float4 n_lo = {0.f, 0.f, 0.f, 0.f}, n_hi = n_lo;
-  if (a_next) n_lo = *reinterpret_cast<const float4*>(a_next), n_hi = *reinterpret_cast<const float4*>(a_next + 8);
-#pragma unroll
-  for (int t = 0; t < NT; ++t) acc[t] = mma6_32(fa, fb[t], acc[t]);
-  if (a_next) fa = split_octets(n_lo, n_hi);
-}
-// Scheduling pattern for a region of N MFMAs with LDS reads and vector work to hide beside them: after each of the
-// first four MFMAs READS_PER LDS reads, after each of the others VALU_PER vector instructions.
-template <int N, int READS_PER, int VALU_PER, int I = 0>
-__device__ __forceinline__ void sched_interleave() {
-  if constexpr (I < N) {
-    __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-    if constexpr (I < 4)
-      __builtin_amdgcn_sched_group_barrier(0x100, READS_PER, 0);
-    else
-      __builtin_amdgcn_sched_group_barrier(0x002, VALU_PER, 0);
-    sched_interleave<N, READS_PER, VALU_PER, I + 1>();
-  }
-}
-// the first fragment of a layer (behind the barrier that completes the image)
-__device__ __forceinline__ x3::Frag first_fragment(const float* __restrict__ a_k) {
-  return split_octets(*reinterpret_cast<const float4*>(a_k), *reinterpret_cast<const float4*>(a_k + 8));
-}
 
 // Phase timing for tools/siren_phases.py (a tools-only build with -DSIREN_PROFILE; the shipped
 // library compiles these to nothing): shader-clock cycles per phase of the forward kernel, per wave.
@@ -925,9 +842,10 @@ __global__ __launch_bounds__(kThreads) void siren_wgrad_kernel(const WgradArgs g
         slab[(n_base + ti * 32 + acc_row(r, lh)) * H + k_base + tj * 32 + l31] = acc[ti][tj][r];
 }
 
-// dst[e] += sum over slabs of partial[slab][e], fixed order
+// dst[e] += sum over slabs of partial[slab][e], fixed order; the slab is a row-major matrix of `cols` columns and
+// dst one of row stride `ld` (ld > cols: the H x H block in front of a modulator layer's (H, H + dim_in) weight)
 __global__ __launch_bounds__(256) void slab_sum_kernel(const float* __restrict__ partial, int slabs,
-                                                       int count, float* __restrict__ dst) {
+                                                       int count, float* __restrict__ dst, int cols, int ld) {
   const int e = blockIdx.x * 256 + threadIdx.x;
   if (e >= count) return;
   const float* p = partial + e;
@@ -941,7 +859,7 @@ __global__ __launch_bounds__(256) void slab_sum_kernel(const float* __restrict__
     for (int j = 0; j < 8; ++j) sum += v[j];
   }
   for (; b < slabs; ++b) sum += p[(int64_t)b * count];
-  dst[e] += sum;
+  dst[ld == cols ? e : (e / cols) * ld + e % cols] += sum;
 }
 
 // Three-term split of the H x H weights into the chunk-major planes issue_chunk streams (layout:
@@ -949,6 +867,8 @@ __global__ __launch_bounds__(256) void slab_sum_kernel(const float* __restrict__
 struct SplitArgs {
   const float* w[kMaxSine];
   int count, H, transposed;
+  int ld;              // row stride of the sources (H, or H + dim_in for a modulator layer's leading block)
+  int64_t out_stride;  // bytes between the planes of consecutive matrices
   char* out;
 };
 
@@ -963,10 +883,10 @@ __global__ __launch_bounds__(256) void siren_split_weights_kernel(const SplitArg
 #pragma unroll
   for (int j = 0; j < 8; ++j) {
     const int k = kKc * kc + 8 * (j >> 2) + 4 * q + (j & 3);
-    v[j] = g.transposed ? w[k * H + row] : w[row * H + k];
+    v[j] = g.transposed ? w[k * g.ld + row] : w[row * g.ld + k];
   }
   const x3::Frag f = x3::split8(v);
-  char* dst = g.out + m * split_matrix_bytes(H) + (int64_t)kc * 3 * H * 32 + row * 32 + 16 * q;
+  char* dst = g.out + m * g.out_stride + (int64_t)kc * 3 * H * 32 + row * 32 + 16 * q;
   *reinterpret_cast<x3::u32x4*>(dst) = f.h;
   *reinterpret_cast<x3::u32x4*>(dst + H * 32) = f.m;
   *reinterpret_cast<x3::u32x4*>(dst + 2 * H * 32) = f.l;
@@ -977,6 +897,7 @@ int split_weights(const float* const* weight, int n_sine, int hidden, bool trans
   if (n_sine < 2) return MRI_OK;
   SplitArgs g{};
   g.count = n_sine - 1, g.H = hidden, g.transposed = transposed ? 1 : 0, g.out = out;
+  g.ld = hidden, g.out_stride = split_matrix_bytes(hidden);
   for (int l = 1; l < n_sine; ++l) g.w[l - 1] = weight[l];
   const int threads = g.count * hidden * (hidden / kKc) * 2;
   hipLaunchKernelGGL(siren_split_weights_kernel, dim3((unsigned)ceil_div(threads, 256)), dim3(256), 0,
@@ -1023,12 +944,12 @@ int launch_backward(const BwdArgs& a, hipStream_t st) {
 }
 
 template <int H>
-int launch_wgrad(const WgradArgs& g, float* d_weight, hipStream_t st) {
+int launch_wgrad(const WgradArgs& g, float* d_weight, hipStream_t st, int ld = H) {
   using W = WgradShape<H>;
   const int wb = wgrad_blocks(g.n);
   hipLaunchKernelGGL((siren_wgrad_kernel<W>), dim3(wb), dim3(kThreads), 0, st, g);
   hipLaunchKernelGGL(slab_sum_kernel, dim3((unsigned)ceil_div(H * H, 256)), dim3(256), 0, st,
-                     g.partial, wb * W::RS, H * H, d_weight);
+                     g.partial, wb * W::RS, H * H, d_weight, H, ld);
   return check_launch("siren_wgrad_kernel");
 }
 
@@ -1100,6 +1021,34 @@ int wgrad_any(int hidden, const WgradArgs& g, float* d_weight, hipStream_t st) {
 }
 
 }  // namespace
+
+// ---- for modsiren.hip (siren_chain.h) ----------------------------------------------------------------------------
+int split_weights_ld(const float* const* w, int count, int hidden, int ld, bool transposed, char* out,
+                     int64_t out_stride, hipStream_t st) {
+  if (count < 1) return MRI_OK;
+  if (count > kMaxSine) return fail(MRI_ERR_INVALID_ARGUMENT, "split_weights_ld: %d matrices", count);
+  SplitArgs g{};
+  g.count = count, g.H = hidden, g.transposed = transposed ? 1 : 0, g.out = out;
+  g.ld = ld, g.out_stride = out_stride;
+  for (int m = 0; m < count; ++m) g.w[m] = w[m];
+  const int threads = count * hidden * (hidden / kKc) * 2;
+  hipLaunchKernelGGL(siren_split_weights_kernel, dim3((unsigned)ceil_div(threads, 256)), dim3(256), 0, st, g);
+  return check_launch("siren_split_weights_kernel");
+}
+
+int wgrad_any_ld(int hidden, const WgradArgs& g, float* d_weight, int ld, hipStream_t st) {
+  switch (hidden) {
+    case 32: return launch_wgrad<32>(g, d_weight, st, ld);
+    case 64: return launch_wgrad<64>(g, d_weight, st, ld);
+    case 128: return launch_wgrad<128>(g, d_weight, st, ld);
+    default: return launch_wgrad<256>(g, d_weight, st, ld);
+  }
+}
+
+int64_t wgrad_slab_floats(int64_t n, int hidden) {
+  return (int64_t)wgrad_blocks(n) * wgrad_split(hidden) * hidden * hidden;
+}
+
 }  // namespace mri
 
 using namespace mri;

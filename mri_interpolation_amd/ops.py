@@ -744,6 +744,127 @@ def siren_backward(x, dy, weights, act, deriv, dz, d_weights, d_biases, head_don
               ws.numel() * 4, _stream())
 
 
+# --------------------------------------------------------------------------- fused modulated SIREN chain
+def modsiren_supported(dim_in: int, hidden: int, n_layers: int, dim_out: int) -> bool:
+    return bool(_lib.load().mri_modsiren_supported(dim_in, hidden, n_layers, dim_out))
+
+
+def modsiren_workspace(n: int, hidden: int, n_layers: int, device) -> torch.Tensor:
+    """Scratch of the three modulated-SIREN calls for batches of up to n rows (partial sums, split weights)."""
+    need = _lib.load().mri_modsiren_backward_workspace_bytes(max(int(n), 1), hidden, n_layers)
+    if need < 0:
+        raise ValueError(f"fused modulated SIREN: hidden {hidden} x {n_layers} layers is not supported")
+    return torch.empty((need + 3) // 4, dtype=torch.float32, device=device)
+
+
+_modsiren_ws = {}
+
+
+def _modsiren_scratch(device, n, hidden, n_layers, ws):
+    if ws is not None:  # the caller's own (FusedStep's, one per batch size): the library checks its size
+        _gpu(ws)
+        return ws
+    need = _lib.load().mri_modsiren_backward_workspace_bytes(max(int(n), 1), hidden, n_layers)
+    if need < 0:  # (the library refuses the shape with its reason)
+        return torch.empty(64, dtype=torch.float32, device=device)
+    ws = _modsiren_ws.get(device.index)
+    if ws is None or ws.numel() * 4 < need:
+        if ws is not None:
+            torch.cuda.synchronize(device)
+        ws = torch.empty((need + 3) // 4, dtype=torch.float32, device=device)
+        _modsiren_ws[device.index] = ws
+    return ws
+
+
+def _modsiren_check(what, n, hidden, n_layers, per_layer, params):
+    for name, seq in per_layer.items():
+        if len(seq) != n_layers:
+            raise ValueError(f"{what}: {name} needs one (n, hidden) buffer per layer")
+        for t in seq:
+            if t is not None and (tuple(t.shape) != (n, hidden) or not t.is_contiguous() or t.dtype != torch.float32):
+                raise ValueError(f"{what}: {name} buffers are contiguous float32 (n, hidden)")
+    for t in params:
+        if not t.is_contiguous() or t.dtype != torch.float32:
+            raise ValueError(f"{what} needs contiguous float32 parameters and buffers")
+
+
+def modsiren_forward(x, siren_weights, siren_biases, mod_weights, mod_biases, w0_first: float, w0: float,
+                     saved=None, y=None, ws=None):
+    """y (n, 1) = ModulatedSirenNet(x) in one persistent kernel (csrc/modsiren.hip).  siren_weights / siren_biases:
+    the SIREN layers' then the head's; mod_weights / mod_biases: the modulator's layers.  saved: None (inference:
+    nothing but y is written) or a dict of four lists act / hid / dcos / sn of per-layer (n, hidden) buffers that
+    receive a_l, h_l, h_l w_l cos(.) and sin(.) for modsiren_backward."""
+    _gpu(x, y, *siren_weights, *siren_biases, *mod_weights, *mod_biases)
+    x = _rowmajor(x).contiguous()
+    n, dim_in = x.shape
+    n_layers, hidden = len(mod_weights), mod_weights[0].shape[0]
+    if len(siren_weights) != n_layers + 1 or len(siren_biases) != n_layers + 1 or len(mod_biases) != n_layers:
+        raise ValueError("modsiren_forward: n_layers + 1 SIREN weights / biases (the head last), n_layers modulator's")
+    if y is None:
+        y = torch.empty((n, 1), device=x.device, dtype=torch.float32)
+    _modsiren_check("modsiren_forward", n, hidden, n_layers, saved or {},
+                    list(siren_weights) + list(siren_biases) + list(mod_weights) + list(mod_biases) + [y])
+    if saved is not None:
+        _gpu(*[t for k in ("act", "hid", "dcos", "sn") for t in saved[k]])
+    ws = _modsiren_scratch(x.device, n, hidden, n_layers, ws)
+    arrays = [_ptr_array(saved[k]) if saved is not None else None for k in ("act", "hid", "dcos", "sn")]
+    _lib.call("mri_modsiren_forward", _ptr(x), n, dim_in, hidden, n_layers, _ptr_array(siren_weights),
+              _ptr_array(siren_biases), _ptr_array(mod_weights), _ptr_array(mod_biases), float(w0_first), float(w0),
+              *arrays, _ptr(y), _ptr(ws), ws.numel() * 4, _stream())
+    return y
+
+
+def modsiren_forward_loss(x, target, siren_weights, siren_biases, mod_weights, mod_biases, w0_first: float,
+                          w0: float, saved, y, dy, loss_out, grad_divisor: float = 1.0, n_total=None, ws=None):
+    """Training forward of the fused modulated SIREN chain with F.mse_loss in the same kernel
+    (mri_modsiren_forward_loss, include/mri_inr.h): dy (n, 1) receives dLoss / dy, loss_out is ADDED to.  Follow with
+    modsiren_backward(x, dy, ...)."""
+    _gpu(x, target, y, dy, loss_out, *siren_weights, *siren_biases, *mod_weights, *mod_biases,
+         *[t for k in ("act", "hid", "dcos", "sn") for t in saved[k]])
+    x = _rowmajor(x).contiguous()
+    n, dim_in = x.shape
+    n_layers, hidden = len(mod_weights), mod_weights[0].shape[0]
+    if len(siren_weights) != n_layers + 1 or len(siren_biases) != n_layers + 1 or len(mod_biases) != n_layers:
+        raise ValueError("modsiren_forward_loss: n_layers + 1 SIREN weights / biases, n_layers modulator's")
+    if target.numel() != n or y.numel() != n or dy.numel() != n:
+        raise ValueError("modsiren_forward_loss: target / y / dy hold n values")
+    _modsiren_check("modsiren_forward_loss", n, hidden, n_layers, saved,
+                    list(siren_weights) + list(siren_biases) + list(mod_weights) + list(mod_biases) + [target, y, dy])
+    ws = _modsiren_scratch(x.device, n, hidden, n_layers, ws)
+    _lib.call("mri_modsiren_forward_loss", _ptr(x), _ptr(target), n, n if n_total is None else n_total, dim_in,
+              hidden, n_layers, _ptr_array(siren_weights), _ptr_array(siren_biases), _ptr_array(mod_weights),
+              _ptr_array(mod_biases), float(w0_first), float(w0), float(grad_divisor),
+              *[_ptr_array(saved[k]) for k in ("act", "hid", "dcos", "sn")], _ptr(y), _ptr(dy), _ptr(loss_out),
+              _ptr(ws), ws.numel() * 4, _stream())
+    return y
+
+
+def modsiren_backward(x, dy, siren_weights, mod_weights, saved, dzs, dzm, d_siren_weights, d_siren_biases,
+                      d_mod_weights, d_mod_biases, ws=None):
+    """Gradients of the fused modulated SIREN chain, ADDED to the four gradient lists (SIREN layers then the head;
+    the modulator's layers).  dy: (n, 1) loss gradient w.r.t. the prediction; saved: what the forward call stored;
+    dzs / dzm: per layer (n, hidden) scratch ([0] may be None)."""
+    _gpu(x, dy, *siren_weights, *mod_weights, *[t for k in ("act", "hid", "dcos", "sn") for t in saved[k]],
+         *[t for t in list(dzs) + list(dzm) if t is not None], *d_siren_weights, *d_siren_biases, *d_mod_weights,
+         *d_mod_biases)
+    x = _rowmajor(x).contiguous()
+    n, dim_in = x.shape
+    n_layers, hidden = len(mod_weights), mod_weights[0].shape[0]
+    if not (len(siren_weights) == len(d_siren_weights) == len(d_siren_biases) == n_layers + 1 and
+            len(d_mod_weights) == len(d_mod_biases) == n_layers):
+        raise ValueError("modsiren_backward: one gradient per parameter (n_layers + 1 SIREN, n_layers modulator)")
+    if dy.numel() != n:
+        raise ValueError("modsiren_backward: dy holds n values")
+    _modsiren_check("modsiren_backward", n, hidden, n_layers, dict(saved, dzs=dzs, dzm=dzm),
+                    list(siren_weights) + list(mod_weights) + list(d_siren_weights) + list(d_siren_biases) +
+                    list(d_mod_weights) + list(d_mod_biases) + [dy])
+    ws = _modsiren_scratch(x.device, n, hidden, n_layers, ws)
+    _lib.call("mri_modsiren_backward", _ptr(x), _ptr(dy), n, dim_in, hidden, n_layers, _ptr_array(siren_weights),
+              _ptr_array(mod_weights), *[_ptr_array(saved[k]) for k in ("act", "hid", "dcos", "sn")],
+              _opt_ptr_array(dzs), _opt_ptr_array(dzm), _ptr_array(d_siren_weights), _ptr_array(d_siren_biases),
+              _ptr_array(d_mod_weights), _ptr_array(d_mod_biases), _ptr(ws), ws.numel() * 4, _stream())
+
+
 # --------------------------------------------------------------------------- loss / optimiser
 def mse_loss(pred, target, loss_out, d_pred=None, grad_divisor: float = 1.0):
     """loss_out[0] += mean((pred - target)^2); d_pred = 2 (pred - target) / (N * divisor)."""

@@ -14,8 +14,12 @@ gradient use the feature-major layout so the hash kernels store/load coalesced.
 The reference's default HashMLP (Linear -> BatchNorm1d -> GELU blocks) has such a chain too, the
 BatchNorm plan (`FusedStep(..., batch_norm=True)`, `Trainer(fused_batchnorm=True)`): per block
 linear_fwd -> bn_stats -> bn_act_forward, and bn_act_backward in front of the Linear's backward
-(csrc/batchnorm.hip).  It is opt-in; without the flag that model runs `training_step` + autograd,
-op by op, as does every model that is no plain chain (ModulatedSirenNet).
+(csrc/batchnorm.hip).  It is opt-in; without the flag that model runs `training_step` + autograd, op by op.
+ModulatedSirenNet is no plain chain but two interleaved stacks; its kernel chain is the modulated plan
+(`FusedStep(..., modulated=True)`, `Trainer(fused_modulated=True)`, csrc/modsiren.hip):
+    modsiren_forward_loss (both stacks of a row tile on chip, loss in the same kernel) -> modsiren_backward
+    (one chain kernel, a slab reduction, two weight-gradient kernels per H x H layer) -> adam
+Opt-in as well: without the flag that model runs `training_step` + autograd over the HIP ops.
 The notebook's HashMLP (two blocks Linear -> GELU, no BatchNorm) takes the shallow plan: `train_step` runs its
 decoder -- forward, loss and backward -- as ONE kernel (csrc/mlp_shallow.hip), `forward(train=True)` + `backward()`
 keep the layer kernels.
@@ -72,13 +76,58 @@ def _batchnorm_layers(model) -> Optional[list]:
     return layers
 
 
-def fusable_layers(model, batch_norm: bool = False) -> Optional[tuple]:
+class ModulatedPlan(tuple):
+    """(None, modulator layers + SIREN layers + head) as every plan, with the two stacks by name: `modulator`
+    [_Layer] * n_layers ((H, d), (H, H + d) ...) and `siren` [_Layer] * (n_layers + 1) ((H, d), (H, H) ..., (1, H))."""
+
+    def __new__(cls, modulator, siren):
+        self = super().__new__(cls, (None, list(modulator) + list(siren)))
+        self.modulator, self.siren = list(modulator), list(siren)
+        return self
+
+
+def _modulated_plan(model) -> ModulatedPlan:
+    """The plan of a ModulatedSirenNet for the kernels of csrc/modsiren.hip; ValueError with the reason for what they
+    do not cover."""
+    what = "fused modulated SIREN step: "
+    sn = model.siren
+    if model.final_activation is not None or sn.last_layer._code is None or sn.last_layer._code[0] != ops.ACT_IDENTITY:
+        raise ValueError(what + "final_activation is set (the kernels end in the linear head)")
+    siren_modules = list(sn.layers) + [sn.last_layer]
+    mod_modules = [seq[0] for seq in model.modulator.layers]
+    if any(l.bias is None for l in siren_modules + mod_modules):
+        raise ValueError(what + "use_bias=False (the kernels take biases everywhere)")
+    for i, l in enumerate(sn.layers):
+        if l._code is None or l._code[0] != ops.ACT_SINE:
+            raise ValueError(what + f"layer {i} has a non-Sine activation ({type(l.activation).__name__})")
+    if any(m.activation_code != ops.ACT_RELU for m in mod_modules):
+        raise ValueError(what + "a modulator layer without ReLU")
+    hidden, dim_in = sn.layers[0].weight.shape
+    n_layers = len(sn.layers)
+    shapes_ok = len(mod_modules) == n_layers and all(
+        tuple(l.weight.shape) == ((hidden, dim_in) if i == 0 else (hidden, hidden)) for i, l in enumerate(sn.layers)) \
+        and all(tuple(m.weight.shape) == ((hidden, dim_in) if i == 0 else (hidden, hidden + dim_in))
+                for i, m in enumerate(mod_modules))
+    dim_out = sn.last_layer.weight.shape[0]
+    if not shapes_ok or tuple(sn.last_layer.weight.shape) != (dim_out, hidden) \
+            or not ops.modsiren_supported(dim_in, hidden, n_layers, dim_out):
+        raise ValueError(what + f"unsupported width or depth: {dim_in} -> {hidden} x {n_layers} -> {dim_out} "
+                         f"(hidden 64 / 128, dim_in <= 8, 2 .. {_lib.MAX_SIREN_LAYERS} layers, one output)")
+    if len({l._code[1] for l in sn.layers[1:]}) > 1:
+        raise ValueError(what + "different w0 among the layers behind the first")
+    return ModulatedPlan([_Layer(m.weight, m.bias, ops.ACT_RELU, 1.0) for m in mod_modules],
+                         [_Layer(l.weight, l.bias, l._code[0], l._code[1]) for l in siren_modules])
+
+
+def fusable_layers(model, batch_norm: bool = False, modulated: bool = False) -> Optional[tuple]:
     """(encoder or None, [_Layer, ...]) if the model is a plain chain of fused layers.  `batch_norm`: also
     accept the reference's BatchNorm decoder blocks of HashMLP (the BatchNorm plan; a BatchNorm decoder the
-    kernels do not cover raises ValueError with the reason)."""
+    kernels do not cover raises ValueError with the reason).  `modulated`: a ModulatedSirenNet gives its
+    ModulatedPlan (both stacks; ValueError with the reason for what csrc/modsiren.hip does not cover)."""
     enc, layers = None, []
     if isinstance(model, models.ModulatedSirenNet):
-        return None  # two interleaved stacks: runs training_step + autograd over the HIP ops
+        # two interleaved stacks: without the keyword it runs training_step + autograd over the HIP ops
+        return _modulated_plan(model) if modulated else None
     if isinstance(model, models.SirenNet):
         for l in list(model.layers) + [model.last_layer]:
             if l._code is None:
@@ -135,8 +184,8 @@ class FusedStep:
     """Explicit forward / backward kernel chain over preallocated workspaces."""
 
     def __init__(self, model, optimizer: optim.Adam, world: int = 1, psf_row_budget: int = 1 << 20,
-                 batch_norm: bool = False):
-        plan = fusable_layers(model, batch_norm=batch_norm)
+                 batch_norm: bool = False, modulated: bool = False):
+        plan = fusable_layers(model, batch_norm=batch_norm, modulated=modulated)
         if plan is None:
             raise ValueError("model is not a fusable chain")
         # BatchNorm plan (csrc/batchnorm.hip): per block linear_fwd -> bn_stats -> bn_act_forward, and
@@ -174,6 +223,12 @@ class FusedStep:
         self.chain = self._siren_chain_plan()
         self.use_chain = self.chain is not None
         self.psf = self._psf_plan(model)
+        # ModulatedSirenNet (csrc/modsiren.hip): both stacks in one forward and one backward chain kernel.  Several
+        # ranks: every gradient lives in the flat buffer, whose one all-reduce in train_step carries it unchanged.
+        # The class's dead default stack (layers.*, last_layer.*) is in the flat buffer too: its gradient stays
+        # zero, so Adam leaves it bit-unchanged.
+        self.modulated = self._modulated_plan(plan) if isinstance(plan, ModulatedPlan) else None
+        self.use_modulated = self.modulated is not None
         # train_step folds the loss and the head's backward into the forward kernel (needs a
         # sine layer below the last one); forward() + backward() keep the separate kernels
         self.chain_loss = self.use_chain and len(self.layers) >= 3
@@ -326,6 +381,54 @@ class FusedStep:
                     w0_first=ls[0].w0, w0=ls[1].w0 if len(ls) > 2 else ls[0].w0,
                     d_weights=[g[0] for g in self._grads], d_biases=[g[1] for g in self._grads])
 
+    def _modulated_plan(self, plan: ModulatedPlan):
+        """Arguments of the modulated SIREN kernels: parameters and the flat buffer's gradient views per stack."""
+        n_mod = len(plan.modulator)
+        sl = plan.siren
+        return dict(sw=[l.weight.data for l in sl], sb=[l.bias.data for l in sl],
+                    mw=[l.weight.data for l in plan.modulator], mb=[l.bias.data for l in plan.modulator],
+                    w0_first=sl[0].w0, w0=sl[1].w0, n_layers=n_mod, hidden=sl[0].weight.shape[0],
+                    d_mw=[g[0] for g in self._grads[:n_mod]], d_mb=[g[1] for g in self._grads[:n_mod]],
+                    d_sw=[g[0] for g in self._grads[n_mod:]], d_sb=[g[1] for g in self._grads[n_mod:]])
+
+    def _modulated_workspace(self, n: int, train: bool):
+        """Inference: the prediction and the split weights only; training: the four saved tensors per layer, the two
+        dz per H x H layer, dLoss/dy and the kernels' scratch."""
+        m, dev = self.modulated, self.flat.param.device
+        new = lambda *s: torch.empty(*s, device=dev, dtype=torch.float32)  # noqa: E731
+        L, H = m["n_layers"], m["hidden"]
+        ws = dict(y=[new(n, 1)])
+        if train:
+            ws["saved"] = {k: [new(n, H) for _ in range(L)] for k in ("act", "hid", "dcos", "sn")}
+            ws["dzs"] = [None] + [new(n, H) for _ in range(L - 1)]
+            ws["dzm"] = [None] + [new(n, H) for _ in range(L - 1)]
+            ws["dy"] = new(n, 1)
+            ws["mod_ws"] = ops.modsiren_workspace(n, H, L, dev)
+        else:
+            need = _lib.load().mri_modsiren_forward_workspace_bytes(H, L)
+            ws["mod_ws"] = torch.empty((need + 3) // 4, dtype=torch.float32, device=dev)
+        return ws
+
+    def _modulated_backward(self, coords, ws):
+        m = self.modulated
+        ops.modsiren_backward(coords, ws["dy"], m["sw"], m["mw"], ws["saved"], ws["dzs"], ws["dzm"], m["d_sw"],
+                              m["d_sb"], m["d_mw"], m["d_mb"], ws=ws["mod_ws"])
+
+    def _modulated_pass(self, coords, target, first, divisor):
+        """forward + loss in one kernel (dLoss/dy leaves with the prediction), then the backward chain."""
+        ws = self._workspace(coords.shape[0], True)
+        m = self.modulated
+        with self._phase("zero_grad"):
+            if first:
+                self.flat.grad.zero_()
+            self.loss.zero_()
+        with self._phase("mlp_fwd"):
+            ops.modsiren_forward_loss(coords, target, m["sw"], m["sb"], m["mw"], m["mb"], m["w0_first"], m["w0"],
+                                      ws["saved"], ws["y"][-1], ws["dy"], self.loss,
+                                      grad_divisor=float(self.world) * float(divisor), ws=ws["mod_ws"])
+        with self._phase("mlp_bwd"):
+            self._modulated_backward(coords, ws)
+
     def _psf_plan(self, model):
         """PsfSirenNet: S, the offset table and the PSF weights beside the chain plan.  Without the chain
         kernels (e.g. dim_hidden 352) there is no fused PSF step: the model trains through training_step."""
@@ -396,6 +499,10 @@ class FusedStep:
     def _workspace(self, n: int, train: bool):
         key = (n, train)
         ws = self._ws.get(key)
+        if ws is None and self.use_modulated:
+            ws = self._modulated_workspace(n, train)
+            self._ws = {k: v for k, v in self._ws.items() if k[1] != train}  # keep one size
+            self._ws[key] = ws
         if ws is None:
             dev = self.flat.param.device
             new = lambda *s: torch.empty(*s, device=dev, dtype=torch.float32)  # noqa: E731
@@ -429,6 +536,12 @@ class FusedStep:
         ws = self._workspace(n, train)
         x, feature_major = coords, False
         self._overlapped = False
+        if self.use_modulated:
+            m = self.modulated
+            with self._phase("mlp_fwd"):
+                ops.modsiren_forward(coords, m["sw"], m["sb"], m["mw"], m["mb"], m["w0_first"], m["w0"],
+                                     saved=ws["saved"] if train else None, y=ws["y"][-1], ws=ws["mod_ws"])
+            return ws["y"][-1], ws
         if self.encoder is not None and train and self.use_tiny and self._overlap_plan(n):
             # lookup on its own stream, queued BEFORE the decoder (which backward() queues on the
             # main stream and which waits for the slices through the ready counters)
@@ -690,6 +803,16 @@ class FusedStep:
         if self.psf is not None:
             raise RuntimeError("PsfSirenNet: its loss is taken through the PSF, train with train_step")
         div = float(self.world) * float(divisor)
+        if self.use_modulated:
+            with self._phase("zero_grad"):
+                if first:
+                    self.flat.grad.zero_()
+                self.loss.zero_()
+            with self._phase("loss"):
+                ops.mse_loss(ws["y"][-1], target, self.loss, ws["dy"], grad_divisor=div)
+            with self._phase("mlp_bwd"):
+                self._modulated_backward(coords, ws)
+            return
         if self.use_tiny:
             # every gradient (tables, decoder) and the loss are OVERWRITTEN by the two kernels
             # below: no zeroing pass over the flat gradient buffer
@@ -873,6 +996,9 @@ class FusedStep:
         if self.psf is not None:
             self._pending = []
             self._psf_pass(coords, target, first, divisor)
+        elif self.use_modulated:
+            self._pending = []
+            self._modulated_pass(coords, target, first, divisor)
         elif self.use_chain and self.chain_loss:
             self._pending = []
             self._chain_loss_pass(coords, target, first, divisor)
@@ -969,6 +1095,8 @@ class SteadyLoop:
             return "PsfSirenNet: the PSF step runs eagerly (FusedStep.train_step), it has no native form"
         if step.bn:
             return "the BatchNorm plan runs eagerly (FusedStep.train_step), it has no native form"
+        if getattr(step, "use_modulated", False):
+            return "ModulatedSirenNet: the modulated plan runs eagerly (FusedStep.train_step), it has no native form"
         if step.world != 1 and (step.dp_mode != "all_reduce" or step.grad_buckets > 1):
             return "several ranks: the plain all-reduce form only (one reduction of the flat gradient)"
         if not (step.use_tiny and step.encoder is not None):
@@ -1210,8 +1338,11 @@ class Trainer:
     def __init__(self, max_epochs: int = 1, max_steps: int = -1, accelerator: str = "gpu",
                  precision: int = 32, log_every: int = 0, distributed: bool = True,
                  accumulate_grad_batches=None, dp_mode: str = "all_reduce", grad_buckets: int = 1,
-                 batch_group: int = 1, native_steps: bool = True, fused_batchnorm: bool = False):
-        """`fused_batchnorm`: train (and predict) the reference's BatchNorm decoder of HashMLP through
+                 batch_group: int = 1, native_steps: bool = True, fused_batchnorm: bool = False,
+                 fused_modulated: bool = False):
+        """`fused_modulated`: train (and predict) a ModulatedSirenNet through FusedStep's modulated plan
+        (csrc/modsiren.hip) instead of training_step + autograd (opt-in, like `fused_batchnorm`).
+        `fused_batchnorm`: train (and predict) the reference's BatchNorm decoder of HashMLP through
         FusedStep's BatchNorm plan instead of training_step + autograd (opt-in; on this path `predict`
         does not collect `model.latents`, as on the other fused paths).
         `accumulate_grad_batches`: an int k (gradients of k consecutive batches are summed,
@@ -1232,6 +1363,7 @@ class Trainer:
         self.batch_group = int(batch_group)    # batches per launch of the on-device producer (BatchPipeline)
         self.native_steps = bool(native_steps)  # queue steady-state steps with one library call (SteadyLoop)
         self.fused_batchnorm = bool(fused_batchnorm)  # FusedStep's BatchNorm plan for the default HashMLP
+        self.fused_modulated = bool(fused_modulated)  # FusedStep's modulated plan for ModulatedSirenNet
         self.rank, self.world = 0, 1
         if distributed:
             rank, world, _ = parallel.env_world()
@@ -1255,7 +1387,8 @@ class Trainer:
             opt = model.configure_optimizers()
             model.optimizer = opt
         try:
-            self.fused = FusedStep(model, opt, self.world, batch_norm=self.fused_batchnorm)
+            self.fused = FusedStep(model, opt, self.world, batch_norm=self.fused_batchnorm,
+                                   modulated=self.fused_modulated)
         except ValueError:
             self.fused = None
             opt.flatten()
@@ -1372,7 +1505,8 @@ class Trainer:
         if fused is None:
             try:
                 fused = FusedStep(model, model.optimizer if hasattr(model, "optimizer")
-                                  else model.configure_optimizers(), 1, batch_norm=self.fused_batchnorm)
+                                  else model.configure_optimizers(), 1, batch_norm=self.fused_batchnorm,
+                                  modulated=self.fused_modulated)
             except ValueError:
                 fused = None
         out = []
