@@ -13,6 +13,11 @@
  *   - `stream` is a hipStream_t passed as void*; calls only enqueue work on it and never
  *     synchronise; the library keeps no global state besides the last-error string;
  *   - all matrices are float32, row-major, with an explicit leading dimension in elements;
+ *   - alignment: every float pointer is 4-byte aligned.  An entry point either takes ANY such pointer and any
+ *     leading dimension (it picks 16-byte accesses where pointer, leading dimension and row count allow them and
+ *     4-byte accesses elsewhere: same values), or names the arguments that must be 16-byte aligned and refuses
+ *     others with MRI_ERR_INVALID_ARGUMENT before anything is queued.  Where nothing is said, any 4-byte aligned
+ *     pointer is served (tests/test_gpu_layout.py);
  *   - return value 0 = success, negative = mri_status; mri_last_error() returns a
  *     thread-local message for the last failure.  No C++ exception crosses this boundary.
  */
@@ -107,12 +112,15 @@ int mri_get_option(const char* name, int32_t* value);
  * (reference encoding.py:108-128, 232-270) incl. fast_hash (encoding.py:69-78), and the
  * torch.cat over levels (encoding.py:190-191, 335-336).
  *   x    (n, D) row-major coordinates.
+ *   table  (sum T_l, F); with F = 2 or 4 it must be 16-byte aligned, else refused: F = 2 rows are read 8 bytes at
+ *        a time ("fwd_pair" 0: two neighbouring rows with one 16-byte load where the level starts at an even
+ *        row), F = 4 rows 16 bytes at a time.
  *   out  element (row i, level l, feature f) is written to
  *        out[l * out_level_stride + i * out_row_stride + f * out_feat_stride].
  *        Reference layout (n, L*F): level stride F, row stride L*F, feature stride 1.
  *        Feature-major layout (L*F, n) used inside the fused trainer (coalesced stores,
  *        read back by mri_linear_forward with x_row_stride 1): level stride F*n, row
- *        stride 1, feature stride n.
+ *        stride 1, feature stride n.  Any 4-byte aligned pointer and any strides.
  */
 int mri_hashgrid_forward(const mri_grid_desc* grid, const float* x, int64_t n,
                          const float* table, float* out, int64_t out_level_stride,
@@ -134,7 +142,7 @@ int mri_hashgrid_forward(const mri_grid_desc* grid, const float* x, int64_t n,
  *   workspace: device scratch of at least mri_hashgrid_backward_workspace_bytes(grid, n)
  *   bytes, 16-byte aligned; no initialisation needed (the call clears what it needs), it
  *   may be shared by calls with different grids / n on the same stream.  May be NULL for
- *   method 1.
+ *   method 1.  x, d_out (any strides) and d_table: any 4-byte aligned pointer.
  */
 int64_t mri_hashgrid_backward_workspace_bytes(const mri_grid_desc* grid, int64_t n);
 /* Optional split: the first stage of the binned backward (counting the records per table
@@ -188,6 +196,8 @@ int mri_hashgrid_backward_adam(const mri_grid_desc* grid, const float* x, const 
  *   deriv (optional, (M, ldd)) receives d act / d z  (w0*cos(w0 z) for sine, gelu'(z));
  *     pass NULL for identity / relu (relu's mask is recovered from y).
  *   w0 is only used by MRI_ACT_SINE.
+ * The four linear entry points take any 4-byte aligned pointers and any strides / leading dimensions: operands
+ * are read, and full output tiles written, 16 bytes at a time where pointer and stride allow it.
  */
 int mri_linear_forward(const float* x, int64_t x_row_stride, int64_t x_col_stride,
                        const float* weight, const float* bias /* may be NULL */, int64_t m,
@@ -220,7 +230,8 @@ int mri_apply_deriv(float* dy, int64_t lddy, int32_t deriv_mode, const float* de
  * `Frequency.forward` (reference encoding.py:43-66): for every row and input axis d,
  * out[d*2L + l] = sin(x_d * 2^l), out[d*2L + L + l] = cos(x_d * 2^l), l = 0..L-1.
  *   x (n, dim) row-major with leading dimension ldx; out (n, dim*2L) with leading dimension ldo.
- * mri_frequency_backward writes (does not accumulate) dx (n, dim) from d_out (n, dim*2L). */
+ * mri_frequency_backward writes (does not accumulate) dx (n, dim) from d_out (n, dim*2L).
+ * 4-byte accesses only: any pointers, any leading dimensions. */
 int mri_frequency_forward(const float* x, int64_t ldx, int64_t n, int32_t dim, int32_t n_levels,
                           float* out, int64_t ldo, void* stream);
 int mri_frequency_backward(const float* x, int64_t ldx, const float* d_out, int64_t ldg, int64_t n,
@@ -243,7 +254,11 @@ int mri_frequency_backward(const float* x, int64_t ldx, const float* d_out, int6
  *   d_x (k_in, n) feature-major = dLoss/dx (optional, may be NULL), y (optional) predictions.
  *   Gradients are those of mean((y - target)^2) / grad_divisor.  Per-workgroup partial sums go
  *   through `workspace` (mri_tiny_mlp_workspace_bytes, no initialisation needed) and are added
- *   in a fixed order: results are bitwise reproducible. */
+ *   in a fixed order: results are bitwise reproducible.
+ * Alignment: x / d_x / y / target and every parameter and gradient pointer may be any 4-byte aligned address (the
+ *   f32-MFMA kernels read x 16 bytes at a time where its address and leading dimension allow it), except that
+ *   the 128-wide f32-MFMA kernel (option "mlp_x3" = 0, and mri_tiny_mlp_train_overlapped) refuses a w2 that is
+ *   not 16-byte aligned. */
 int mri_tiny_mlp_supported(int32_t k_in, int32_t hidden, int32_t dim_out);
 int64_t mri_tiny_mlp_workspace_bytes(int32_t k_in, int32_t hidden, int64_t n);
 int mri_tiny_mlp_forward(const float* x, int64_t n, int32_t k_in, int32_t hidden, const float* w1,
@@ -311,7 +326,7 @@ int mri_hashgrid_backward_scaled(const mri_grid_desc* grid, const float* x, cons
  * d_enc.  Grids with n_features = 2, dim 2..4, <= 16 levels, < 2^29 table rows; hidden 64 or 128
  * (mri_hash_tiny_mlp_supported, else MRI_ERR_UNSUPPORTED).  coords (n, dim) row-major; d_enc
  * (2 L, d_enc_ld) feature-major = dLoss / d features, the input of mri_hashgrid_backward; workspace as
- * mri_tiny_mlp_workspace_bytes(2 L, hidden, n). */
+ * mri_tiny_mlp_workspace_bytes(2 L, hidden, n).  table must be 16-byte aligned (as for mri_hashgrid_forward). */
 int mri_hash_tiny_mlp_supported(const mri_grid_desc* grid, int32_t hidden);
 int mri_hash_tiny_mlp_train(const mri_grid_desc* grid, const float* table, const float* coords,
                             const float* target, int64_t n, int32_t hidden, const float* w1,
@@ -339,7 +354,7 @@ int mri_hash_tiny_mlp_train(const mri_grid_desc* grid, const float* table, const
  *   Per-workgroup partial sums go through `workspace` (mri_shallow_mlp_workspace_bytes, -1 for an
  *   unsupported shape; no initialisation needed) and are added in a fixed order: bitwise reproducible.
  * n = 0 is a no-op; NULL buffers, an unsupported shape or a short workspace return
- * MRI_ERR_INVALID_ARGUMENT before anything is queued. */
+ * MRI_ERR_INVALID_ARGUMENT before anything is queued.  4-byte accesses to every caller buffer: any pointers. */
 int mri_shallow_mlp_supported(int32_t k_in, int32_t hidden, int32_t dim_out, int32_t act_hidden,
                               int32_t act_out);
 int64_t mri_shallow_mlp_workspace_bytes(int32_t k_in, int32_t hidden, int64_t n);
@@ -373,7 +388,10 @@ int mri_hashgrid_backward_input(const mri_grid_desc* grid, const float* x, const
  * it as ready_target).  mri_tiny_mlp_train_overlapped is mri_tiny_mlp_train[_overwrite] whose
  * workgroups wait for ready[r] >= ready_target before touching round r's rows (bounded wait: a
  * producer that never arrives sets *status = 1 instead of hanging the GPU).  Same results as the
- * two plain calls, bit for bit.  Needs n_features == 2, 2 <= dim <= 4, hidden == 128. */
+ * two plain calls, bit for bit.  Needs n_features == 2, 2 <= dim <= 4, hidden == 128.
+ * mri_hashgrid_forward_signal takes any slice_rows >= 1, any out pointer and any out_ld >= n (table as for
+ * mri_hashgrid_forward): a slice is stored 16 bytes at a time where out is 16-byte aligned, out_ld % 4 == 0 and the
+ * slice starts at a multiple of 4 rows (every slice when slice_rows % 4 == 0), 4 bytes at a time elsewhere. */
 int64_t mri_hashgrid_forward_signal_blocks(const mri_grid_desc* grid, int64_t slice_rows);
 int mri_hashgrid_forward_signal(const mri_grid_desc* grid, const float* x, int64_t n,
                                 const float* table, float* out, int64_t out_ld,
@@ -399,9 +417,12 @@ int mri_tiny_mlp_train_overlapped(const float* x, const float* target, int64_t n
  * (mri_siren_supported); other shapes go layer by layer through mri_linear_*.
  * weight / bias: HOST arrays of n_sine_layers + 1 device pointers -- [0] (hidden, dim_in),
  * [1 .. n-1] (hidden, hidden), [n] the head (1, hidden); all row-major, 16-byte aligned.
- * act / deriv: HOST arrays of n_sine_layers device pointers to (n, hidden) row-major buffers that
- * receive each sine layer's output and its derivative w0 cos(.) for the backward pass, or both
+ * act / deriv: HOST arrays of n_sine_layers device pointers to (n, hidden) row-major, 16-byte aligned buffers
+ * that receive each sine layer's output and its derivative w0 cos(.) for the backward pass, or both
  * NULL (inference: nothing but y is written).  y: (n) predictions.
+ * Alignment (the three SIREN calls): weight[l], act[l], deriv[l], dz[l], dz_last and workspace must be 16-byte
+ * aligned, else MRI_ERR_INVALID_ARGUMENT names the argument; x, y, target, dy, the biases and every gradient
+ * output are accessed 4 bytes at a time.
  * workspace: mri_siren_forward_workspace_bytes device bytes, 16-byte aligned (0 bytes / NULL with one
  * sine layer): each call first splits the hidden x hidden weights there into the three bf16 terms
  * the matrix pipe multiplies (f32-accurate, csrc/bf16x3.h), in the order the kernel streams them. */
@@ -462,6 +483,7 @@ int mri_siren_forward_loss(const float* x, const float* target, int64_t n, int64
  * [0] (hidden, dim_in), [l] (hidden, hidden + dim_in), the hidden columns first (the reference concatenates
  * (hidden, z)).  All row-major and contiguous.
  * act / hid / dcos / sn: HOST arrays of n_layers device pointers to (n, hidden) row-major, 16-byte aligned buffers
+ * (checked by all three calls, as dzs / dzm and the workspace are; every other pointer: any 4-byte aligned address)
  * that receive, per layer, a_l = s_l h_l, h_l, h_l w_l cos(.) and s_l = sin(.) for the backward pass -- or all four
  * NULL (inference: nothing but y is written).  y: (n) predictions.
  * workspace: mri_modsiren_forward_workspace_bytes device bytes, 16-byte aligned: each call first splits the hidden x
@@ -514,7 +536,8 @@ int mri_modsiren_backward(const float* x, const float* dy, int64_t n, int32_t di
  * mri_psf_mse_loss (training_step, models.py:529-537: psf_conv, then F.mse_loss(z, y)): zbar_out (n)
  *   receives the reduced values, loss_out[0] += sum_b (zbar_b - y_b)^2 / n_total (ADDED; the caller zeroes),
  *   dz (n*S) = w_k * 2 (zbar_b - y_b) / (n_total * grad_divisor) (written; NULL: no gradient).  n <= n_total:
- *   a slice of n whole targets of a batch of n_total, as mri_siren_forward_loss. */
+ *   a slice of n whole targets of a batch of n_total, as mri_siren_forward_loss.
+ * Any 4-byte aligned pointers (mri_psf_expand stores 16 bytes at a time where x_psf is 16-byte aligned). */
 int mri_psf_expand(const float* x, int64_t n, int32_t dim_in, const float* offsets, int32_t S,
                    float* x_psf, void* stream);
 int mri_psf_reduce(const float* in, int64_t n, int32_t S, int32_t C, const float* w, float* out,
@@ -543,7 +566,10 @@ int mri_psf_mse_loss(const float* z, const float* target, int64_t n, int64_t n_t
  * mri_bn_act_backward (autograd of the same): g = dy * act'(u), dbeta = sum g, dgamma = sum g xhat,
  *   dz = gamma invstd (g - dbeta / n - xhat dgamma / n); xhat and u are recomputed from z and save with the
  *   forward's expressions (nothing else is kept for the backward).  d_gamma / d_beta are written
- *   (overwrite != 0) or added to; dz may alias dy (same leading dimension), not z. */
+ *   (overwrite != 0) or added to; dz may alias dy (same leading dimension), not z.
+ * The matrices (z, y, dy, dz) may be any 4-byte aligned pointers with any leading dimension >= C (16-byte accesses
+ * when all matrices of a call are 16-byte aligned, their leading dimensions and C multiples of 4); gamma, beta,
+ * save, the running buffers and the gradients are read and written float by float. */
 int64_t mri_bn_workspace_bytes(int64_t n, int32_t C);
 int mri_bn_stats(const float* z, int64_t ldz, int64_t n, int32_t C, double momentum, double eps,
                  float* running_mean, float* running_var, int64_t* num_batches_tracked, float* save,
@@ -560,7 +586,7 @@ int mri_bn_act_backward(const float* dy, int64_t lddy, const float* z, int64_t l
  * F.mse_loss(y, y_pred) (reference models.py:64): loss_out[0] += mean((pred-target)^2)
  * (device scalar, caller zeroes), d_pred = 2 (pred - target) / (count * grad_divisor) if
  * d_pred != NULL.  pred/target/d_pred are contiguous with `count` elements.
- * grad_divisor > 1 pre-averages gradients over data-parallel ranks. */
+ * grad_divisor > 1 pre-averages gradients over data-parallel ranks.  4-byte accesses: any pointers. */
 int mri_mse_loss(const float* pred, const float* target, int64_t count, float grad_divisor,
                  float* loss_out, float* d_pred, void* stream);
 
@@ -591,7 +617,9 @@ int mri_adam_step(float* param, const float* grad, float* exp_avg, float* exp_av
  * time than GPU time on a slow host.  One launch fewer than the separate calls: with n_params > 0
  * the table gradient's last conversion (int64 sums -> f32, bin_finalize_kernel) is done by the Adam kernel as it
  * fetches the gradient (the same expression: the same bits) -- `d_table` then does NOT hold the gradient of those
- * levels after the call. */
+ * levels after the call.  That fold needs param / grad / exp_avg / exp_avg_sq 16-byte aligned; other ranges (one
+ * 4-byte aligned offset within a 16-byte line, as mri_adam_step asks) run the conversion launch and mri_adam_step:
+ * the same bits.  `table` as for mri_hashgrid_forward, checked at the top of the call, before anything is queued. */
 typedef struct mri_fused_step_args {
   const mri_grid_desc* grid;
   float* table;                                  /* (sum T_l, F), inside the flat parameter buffer */
@@ -643,7 +671,7 @@ int64_t mri_fused_step_args_bytes(void); /* sizeof(mri_fused_step_args): lets a 
  * mri_gather_batch: flat C-order voxel index -> coordinates (row-major (n, D)) through the
  *   per-axis linspace tables (`axes` = concatenation of the D axis arrays built with
  *   torch.linspace on the host, axis_offset[d] = start of axis d) and targets from `volume`.
- *   shape / axis_offset are HOST arrays of length D. */
+ *   shape / axis_offset are HOST arrays of length D.  4-byte (idx: 8-byte) accesses: any such pointers. */
 int mri_sample_indices(uint64_t seed, int64_t first, int64_t lo, int64_t hi, int64_t n,
                        int64_t* idx_out, void* stream);
 int mri_gather_batch(const int64_t* idx, int64_t n, int32_t dim, const int64_t* shape,

@@ -48,6 +48,8 @@ extern "C" int mri_fused_step(const mri_fused_step_args* a) {
   MRI_REQUIRE(a->n >= 1 && a->stream_side && a->ev_fork && a->ev_join, "fused step: n >= 1, a side stream and two events");
   for (int i = 1; i < 5; ++i)
     MRI_REQUIRE((a->ev_phase[i] != nullptr) == (a->ev_phase[0] != nullptr), "fused step: five phase events or none");
+  // (refused here, before the side stream's launches, not by the lookup in the middle of the step)
+  MRI_REQUIRE(a->table && table_aligned(a->grid, a->table), kTableAlignment);
   hipStream_t main = (hipStream_t)a->stream, side = (hipStream_t)a->stream_side;
   hipEvent_t fork = (hipEvent_t)a->ev_fork, join = (hipEvent_t)a->ev_join;
   TRACE_BEGIN

@@ -67,6 +67,8 @@ __global__ __launch_bounds__(256) void hashgrid_fwd_kernel(
   float acc[F];
 #pragma unroll
   for (int f = 0; f < F; ++f) acc[f] = 0.0f;
+  // (a level that starts at an odd row of a two-feature table is 8-byte aligned only: pairs one by one)
+  const bool pair16 = (reinterpret_cast<uintptr_t>(rows) & 15) == 0;
   if constexpr (F == 2) {
     // The two corners that differ only on axis 0 (PRIME_0 = 1) hash to h and h ^ (x ^ (x+1)):
     // for an even cell index the slots are 2k and 2k+1, i.e. one aligned 16-byte pair of rows.
@@ -80,7 +82,7 @@ __global__ __launch_bounds__(256) void hashgrid_fwd_kernel(
       corner<D>(c, nb + 1, h1, w1);
       const uint32_t s0 = slot_of(h0, size, magic, pow2), s1 = slot_of(h1, size, magic, pow2);
       float2 v0, v1;
-      if ((s0 ^ 1u) == s1) {
+      if (pair16 && (s0 ^ 1u) == s1) {
         const float4 t = *reinterpret_cast<const float4*>(rows + (uint64_t)(s0 & ~1u) * 2);
         const float2 lo = make_float2(t.x, t.y), hi = make_float2(t.z, t.w);
         v0 = (s0 & 1u) ? hi : lo;
@@ -214,7 +216,10 @@ __global__ __launch_bounds__(256) void hashgrid_fwd_pair_signal_kernel(
   const bool pow2 = tab.pow2[level] != 0;
   const float* __restrict__ rows_p = table + tab.offset[level] * 2;
   const int xc = threadIdx.x & 1;
-  const bool aligned = (ld & 3) == 0 && (reinterpret_cast<uintptr_t>(out) & 15) == 0;
+  // 16-byte stores need the slice to start on a quad of columns as well: a quad that begins in front of row0
+  // has its storing lane in the previous slice's block, and one that straddles a wave (32 coordinates from
+  // row0 on) cannot be collected by the shuffles below.  Such slices (slice_rows % 4 != 0) store 4 bytes a lane.
+  const bool aligned = (ld & 3) == 0 && (row0 & 3) == 0 && (reinterpret_cast<uintptr_t>(out) & 15) == 0;
   for (int sub = 0; sub < kSignalChunks; ++sub) {
     const int64_t c0 = ((int64_t)chunk * kSignalChunks + sub) * 128;
     if (chunk >= sched.chunks || c0 >= rows) break;  // block-uniform
@@ -433,6 +438,7 @@ extern "C" int mri_hashgrid_forward(const mri_grid_desc* grid, const float* x, i
   MRI_REQUIRE(n >= 0 && n < (1ll << 31), "n = %lld out of range", (long long)n);
   if (n == 0) return MRI_OK;
   MRI_REQUIRE(x && table && out, "NULL device pointer");
+  MRI_REQUIRE(table_aligned(grid, table), kTableAlignment);
   const LevelTab tab = make_tab(grid);
   const Sched sched = make_sched(grid->n_levels, n);
   MRI_REQUIRE(grid_blocks(sched) < (1ll << 31), "grid too large");
@@ -458,6 +464,7 @@ extern "C" int mri_hashgrid_forward_signal(const mri_grid_desc* grid, const floa
   MRI_REQUIRE(slice_rows >= 1, "slice_rows %lld", (long long)slice_rows);
   if (n == 0) return MRI_OK;
   MRI_REQUIRE(x && table && out && ready && out_ld >= n, "NULL device pointer / short leading dimension");
+  MRI_REQUIRE(table_aligned(grid, table), kTableAlignment);
   const LevelTab tab = make_tab(grid);
   Sched sched = make_sched(grid->n_levels, slice_rows, 128 * kSignalChunks);
   sched.affinity = 1;  // the block order inside a slice is the XCD-aware one

@@ -124,6 +124,14 @@ inline int validate(const mri_grid_desc* g) {
   return MRI_OK;
 }
 
+// The lookups read a row of two features with one 8-byte load (two neighbouring rows with one 16-byte load where the
+// level starts on a 16-byte boundary) and a row of four features with one 16-byte load: such tables start on a
+// 16-byte boundary.  One- and eight-feature rows are read float by float.
+inline bool table_aligned(const mri_grid_desc* g, const float* table) {
+  return (g->n_features != 2 && g->n_features != 4) || (reinterpret_cast<uintptr_t>(table) & 15) == 0;
+}
+constexpr const char* kTableAlignment = "table must be 16-byte aligned (grids of 2 or 4 features per level)";
+
 inline LevelTab make_tab(const mri_grid_desc* g) {
   LevelTab t{};
   for (int l = 0; l < g->n_levels; ++l) {

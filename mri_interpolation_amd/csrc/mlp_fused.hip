@@ -1120,6 +1120,7 @@ extern "C" int mri_hash_tiny_mlp_train(const mri_grid_desc* grid, const float* t
   if (n == 0) return MRI_OK;
   const int k_in = 2 * grid->n_levels;
   MRI_REQUIRE(table && coords && target && w1 && b1 && w2 && b2 && w3 && b3, "NULL device pointer");
+  MRI_REQUIRE(table_aligned(grid, table), kTableAlignment);
   MRI_REQUIRE(d_w1 && d_b1 && d_w2 && d_b2 && d_w3 && d_b3 && loss_out, "NULL gradient pointer");
   MRI_REQUIRE(!d_enc || d_enc_ld >= n, "d_enc rows are %lld apart, batch of %lld", (long long)d_enc_ld,
               (long long)n);

@@ -643,6 +643,9 @@ int fill_forward(ModArgs& a, const float* x, int64_t n, int dim_in, int hidden, 
     MRI_REQUIRE(act && hid && dcos && sn, "training needs the act / hid / dcos / sn buffer arrays");
     for (int l = 0; l < L; ++l) {
       MRI_REQUIRE(act[l] && hid[l] && dcos[l] && sn[l], "NULL saved-tensor buffer (layer %d)", l);
+      // (the backward's weight-gradient kernels stream act / hid in 16-byte pieces: one contract for the four, here too)
+      MRI_REQUIRE(aligned16(act[l]) && aligned16(hid[l]) && aligned16(dcos[l]) && aligned16(sn[l]),
+                  "act / hid / dcos / sn buffers must be 16-byte aligned (layer %d)", l);
       a.act[l] = act[l], a.hid[l] = hid[l], a.dcos[l] = dcos[l], a.sn[l] = sn[l];
     }
   }
@@ -754,8 +757,10 @@ extern "C" int mri_modsiren_backward(const float* x, const float* dy, int64_t n,
                 "NULL modulator parameter / gradient pointer (layer %d)", l);
     MRI_REQUIRE(act[l] && hid[l] && dcos[l] && sn[l] && (l == 0 || (dzs[l] && dzm[l])),
                 "NULL saved-tensor buffer (layer %d)", l);
-    MRI_REQUIRE(aligned16(act[l]) && aligned16(hid[l]) && (l == 0 || (aligned16(dzs[l]) && aligned16(dzm[l]))),
-                "activation buffers must be 16-byte aligned (layer %d)", l);
+    MRI_REQUIRE(aligned16(act[l]) && aligned16(hid[l]) && aligned16(dcos[l]) && aligned16(sn[l]),
+                "act / hid / dcos / sn buffers must be 16-byte aligned (layer %d)", l);
+    MRI_REQUIRE(l == 0 || (aligned16(dzs[l]) && aligned16(dzm[l])), "dzs / dzm buffers must be 16-byte aligned (layer %d)",
+                l);
     r.d_wm[l] = d_mod_weight[l], r.d_bm[l] = d_mod_bias[l];
     a.hid[l] = hid[l], a.dcos[l] = dcos[l], a.sn[l] = sn[l], a.dzs[l] = dzs[l], a.dzm[l] = dzm[l];
   }

@@ -1053,6 +1053,13 @@ int64_t wgrad_slab_floats(int64_t n, int hidden) {
 
 using namespace mri;
 
+namespace {
+// The (n, hidden) tensors leave and return in 16-byte pieces: the rows kernels (hidden 256) store act / deriv / dz_last
+// four floats a lane, the weight-gradient kernels stream act and dz into LDS sixteen bytes a lane.
+bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+constexpr const char* kActAlignment = "act / deriv buffers must be 16-byte aligned (layer %d)";
+}  // namespace
+
 extern "C" int mri_siren_supported(int32_t dim_in, int32_t hidden, int32_t n_sine_layers,
                                    int32_t dim_out) {
   return chain_supported(dim_in, hidden, n_sine_layers, dim_out) ? 1 : 0;
@@ -1087,6 +1094,7 @@ extern "C" int mri_siren_forward(const float* x, int64_t n, int32_t dim_in, int3
   if (act)
     for (int l = 0; l < n_sine_layers; ++l) {
       MRI_REQUIRE(act[l] && deriv[l], "NULL activation buffer (layer %d)", l);
+      MRI_REQUIRE(aligned16(act[l]) && aligned16(deriv[l]), kActAlignment, l);
       a.act[l] = act[l], a.deriv[l] = deriv[l];
     }
   a.wsplit = static_cast<const char*>(workspace);
@@ -1167,8 +1175,10 @@ extern "C" int mri_siren_forward_loss(const float* x, const float* target, int64
   }
   for (int l = 0; l + 1 < n_sine_layers; ++l) {  // the last sine layer's a / w0 cos stay on chip
     MRI_REQUIRE(act[l] && deriv[l], "NULL activation buffer (layer %d)", l);
+    MRI_REQUIRE(aligned16(act[l]) && aligned16(deriv[l]), kActAlignment, l);
     a.act[l] = act[l], a.deriv[l] = deriv[l];
   }
+  MRI_REQUIRE(aligned16(dz_last), "dz_last must be 16-byte aligned");
   hipStream_t st = (hipStream_t)stream;
   a.wsplit = wsplit;
   remember_loss_call(LossCall{workspace, dz_last, n, hidden, n_sine_layers,
@@ -1238,9 +1248,8 @@ extern "C" int mri_siren_backward(const float* x, const float* dy, int64_t n, in
     const bool on_chip = head_done && l == L - 1;  // the loss-mode forward never stored these
     MRI_REQUIRE((on_chip || (act[l] && deriv[l])) && (l == 0 || dz[l]),
                 "NULL activation buffer (layer %d)", l);
-    MRI_REQUIRE((on_chip || (reinterpret_cast<uintptr_t>(act[l]) & 15) == 0) &&
-                    (l == 0 || (reinterpret_cast<uintptr_t>(dz[l]) & 15) == 0),
-                "activation buffers must be 16-byte aligned");
+    MRI_REQUIRE(on_chip || (aligned16(act[l]) && aligned16(deriv[l])), kActAlignment, l);
+    MRI_REQUIRE(l == 0 || aligned16(dz[l]), "dz buffers must be 16-byte aligned (layer %d)", l);
     a.deriv[l] = on_chip ? nullptr : deriv[l];
     a.dz[l] = dz[l];
   }
