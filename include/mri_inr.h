@@ -469,6 +469,27 @@ int mri_siren_forward_loss(const float* x, const float* target, int64_t n, int64
                            float* d_b_last, float* loss_out, void* workspace,
                            int64_t workspace_bytes, void* stream);
 
+/* Values AND the gradient with respect to the coordinates of the same network, y (n) and dydx (n, dim_in)
+ * row-major, dydx[i, d] = d y[i] / d x[i, d], in ONE persistent kernel (csrc/siren_gradient.hip): forward mode --
+ * the tangent of sine layer l is w_l cos(w_l z_l) (.) (tangent of layer l - 1) W_l^T, the value row's product on
+ * more rows --, so a point travels as four consecutive rows of the LDS activation image (value, d/dx_0, d/dx_1,
+ * d/dx_2) through the tile loop of mri_siren_forward's inference kernel; the hidden x hidden products run on the
+ * same bf16x3 form.  Nothing (n, hidden)-sized is written: the call reads n dim_in floats and writes n (1 + dim_in).
+ * No atomics, a fixed summation order: bitwise reproducible.  At most 256 workgroups walk the tiles of 1024 / hidden
+ * points (64 at hidden 32).
+ * Supported (mri_siren_gradient_supported is the truth): hidden in {32, 64, 128, 256}, 1 <= dim_in <= 3,
+ * 1 <= n_sine_layers <= MRI_SIREN_MAX_LAYERS, dim_out = 1; anything else is refused with MRI_ERR_INVALID_ARGUMENT,
+ * the offending argument named in mri_last_error.  n = 0 returns 0 without a launch.
+ * weight / bias: as mri_siren_forward (weight[l] 16-byte aligned); x, y and dydx are accessed 4 bytes at a time at
+ * any 4-byte aligned address.  workspace: mri_siren_gradient_workspace_bytes device bytes (what
+ * mri_siren_forward_workspace_bytes reports: the split weights; -1 for an unsupported width or depth), 16-byte
+ * aligned, 0 bytes / NULL with one sine layer. */
+int mri_siren_gradient_supported(int32_t dim_in, int32_t hidden, int32_t n_sine_layers, int32_t dim_out);
+int64_t mri_siren_gradient_workspace_bytes(int32_t hidden, int32_t n_sine_layers);
+int mri_siren_gradient(const float* x, int64_t n, int32_t dim_in, int32_t hidden, int32_t n_sine_layers,
+                       const float* const* weight, const float* const* bias, float w0_first, float w0, float* y,
+                       float* dydx, void* workspace, int64_t workspace_bytes, void* stream);
+
 /* ---- fused modulated SIREN chain ---------------------------------------------------------------
  * ModulatedSirenNet.forward (reference models.py:263-322): per layer l the SIREN layer sin(w_l (a_{l-1} Ws_l^T +
  * bs_l)) (SirenLayer.forward, models.py:153-156; w_0 = w0_first) multiplied elementwise by the modulator's hidden

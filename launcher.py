@@ -76,6 +76,10 @@ def parse_args(argv=None):
     p.add_argument("--accelerator", choices=("auto", "gpu", "cpu"), default="auto",
                    help="auto: the MI355X path if a GPU is visible, else the PyTorch-CPU plumbing mode (SirenNet only; "
                         "reference launcher.py:157: accelerator='gpu' if torch.cuda.is_available() else 'cpu')")
+    p.add_argument("--save_gradient", action="store_true",
+                   help="after pred.nii.gz also write gradient.nii.gz, float32 of shape image_shape + (dim_in,): the "
+                        "change of the network's output per voxel step along each axis (models with one output; "
+                        "SirenNet / PsfSirenNet through the fused gradient kernel, the others through autograd)")
     p.add_argument("--out_dir", type=str, default=None)
     p.add_argument("--max_steps", type=int, default=-1)
     p.add_argument("--log_every", type=int, default=50)
@@ -89,6 +93,33 @@ def psf_spacing(shape, k, norm_siren=True):
     one voxel gets 0."""
     lo = -1.0 if norm_siren else 0.0
     return tuple((1.0 - lo) / (s - 1) / 2 if s > 1 else 0.0 for s in list(shape)[:k])
+
+
+def gradient_voxel_scale(shape, norm_siren=True):
+    """Per axis, the coordinate step between neighbouring voxels in the loader's coordinates (linspace(lo, 1, s),
+    lo = -1 under norm_siren, else 0): dy/dx times it is the change of the network's output per voxel step along
+    that axis, what --save_gradient writes.  An axis of one voxel gets 0."""
+    lo = -1.0 if norm_siren else 0.0
+    return tuple((1.0 - lo) / (s - 1) if s > 1 else 0.0 for s in list(shape))
+
+
+def check_save_gradient(model_cls, dim_out):
+    """--save_gradient ends here, before any training, for a model that cannot serve it."""
+    if not callable(getattr(model_cls, "forward_with_gradient", None)):
+        raise SystemExit(f"--save_gradient: {model_cls.__name__} has no forward_with_gradient")
+    if dim_out != 1:
+        raise SystemExit(f"--save_gradient needs a model with one output (dim_out = {dim_out}): the gradient "
+                         "volume holds the derivative of ONE value per axis")
+
+
+def save_gradient_volume(dydx, config, out_dir, nifti):
+    """gradient.nii.gz: dydx (N, dim_in) in grid order -> image_shape + (dim_in,), in output units per voxel step."""
+    import numpy as np
+    scale = np.asarray(gradient_voxel_scale(config.image_shape, config.norm_siren), dtype=np.float32)
+    grad = np.asarray(dydx.detach().cpu().numpy(), dtype=np.float32) * scale
+    grad = np.ascontiguousarray(grad.reshape(tuple(config.image_shape) + (config.dim_in,)), dtype=np.float32)
+    nifti.save(grad, os.path.join(out_dir, "gradient.nii.gz"))
+    return grad
 
 
 def apply_decoder_flags(config, args):
@@ -157,14 +188,14 @@ def main(argv=None):
     overrides = {k: v for k, v in vars(args).items()
                  if k not in ("synthetic", "tiny_mlp", "no_batchnorm", "out_dir", "max_steps", "log_every",
                               "resume_optimizer", "restore_lr", "unsafe_checkpoint", "accelerator",
-                              "enco_config_path", "holdout_odd_frames", "base_resolution",
+                              "enco_config_path", "holdout_odd_frames", "base_resolution", "save_gradient",
                               "finest_resolution")}
     cfg.apply_overrides(config, overrides)
 
     # ---- data ---------------------------------------------------------------------------
     if args.synthetic:
         shape = tuple(int(s) for s in args.synthetic.split(","))
-        volume = datamodules.phantom_volume(shape).cpu().numpy()
+        volume = datamodules.phantom_volume(shape, device="cpu" if use_cpu else "cuda").cpu().numpy()
     else:
         volume = nifti.load(config.image_path)
         if config.slice_spec:
@@ -189,6 +220,8 @@ def main(argv=None):
                          f"{config.dim_in}-D volume (SURVEY.md Q7): pass --slice, --tiny_mlp or "
                          "--base_resolution / --finest_resolution with one value per axis")
     config.norm_siren = config.model_class in ("SirenNet", "ModulatedSirenNet", "PsfSirenNet")
+    if args.save_gradient:
+        check_save_gradient(getattr(models, config.model_class), config.dim_out)
     if use_cpu:
         return main_cpu(args, config, volume)
 
@@ -258,6 +291,9 @@ def main(argv=None):
     if im.ndim == 2:
         np.save(os.path.join(out_dir, "pred.npy"), im)
     nifti.save(im, os.path.join(out_dir, "pred.nii.gz"))
+    if args.save_gradient:
+        _, grads = trainer.predict_with_gradient(model, test_loader)
+        save_gradient_volume(torch.concat(grads), config, out_dir, nifti)
 
     for shape in config.interp_shapes:
         if len(shape) != config.dim_in:
@@ -315,6 +351,8 @@ def main_cpu(args, config, volume):
     if im.ndim == 2:
         np.save(os.path.join(out_dir, "pred.npy"), im)
     nifti.save(im, os.path.join(out_dir, "pred.nii.gz"))
+    if args.save_gradient:
+        save_gradient_volume(cpu_path.predict_with_gradient(model, coords, config.batch_size)[1], config, out_dir, nifti)
     for shape in config.interp_shapes:
         if len(shape) != config.dim_in:
             print(f"skip interpolation shape {shape}: volume is {config.dim_in}-D")

@@ -109,6 +109,7 @@ SIGNATURES = {
     "mri_siren_forward_loss": [_P, _P, _I64, _I64, _I32, _I32, _I32, C.POINTER(_P), C.POINTER(_P), _F,
                                _F, _F, C.POINTER(_P), C.POINTER(_P), _P, _P, _P, _P, _P, _P, _P,
                                _I64, _P],
+    "mri_siren_gradient": [_P, _I64, _I32, _I32, _I32, C.POINTER(_P), C.POINTER(_P), _F, _F, _P, _P, _P, _I64, _P],
     "mri_modsiren_forward": [_P, _I64, _I32, _I32, _I32] + [C.POINTER(_P)] * 4 + [_F, _F] + [C.POINTER(_P)] * 4
                             + [_P, _P, _I64, _P],
     "mri_modsiren_forward_loss": [_P, _P, _I64, _I64, _I32, _I32, _I32] + [C.POINTER(_P)] * 4 + [_F, _F, _F]
@@ -138,6 +139,7 @@ INT64_GETTERS = {"mri_hashgrid_backward_workspace_bytes": [C.POINTER(GridDesc), 
                  "mri_bn_workspace_bytes": [_I64, _I32],
                  "mri_siren_backward_workspace_bytes": [_I64, _I32, _I32],
                  "mri_siren_forward_workspace_bytes": [_I32, _I32],
+                 "mri_siren_gradient_workspace_bytes": [_I32, _I32],
                  "mri_modsiren_backward_workspace_bytes": [_I64, _I32, _I32],
                  "mri_modsiren_forward_workspace_bytes": [_I32, _I32],
                  "mri_hashgrid_forward_signal_blocks": [C.POINTER(GridDesc), _I64],
@@ -147,6 +149,7 @@ INT_GETTERS = {"mri_tiny_mlp_supported": [_I32, _I32, _I32],
                "mri_hash_tiny_mlp_supported": [C.POINTER(GridDesc), _I32],
                "mri_tiny_mlp_dx_absmax_supported": [_I32, _I32],
                "mri_siren_supported": [_I32, _I32, _I32, _I32],
+               "mri_siren_gradient_supported": [_I32, _I32, _I32, _I32],
                "mri_modsiren_supported": [_I32, _I32, _I32, _I32]}  # return a plain value, not a status
 
 _lib = None

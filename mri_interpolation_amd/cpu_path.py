@@ -75,6 +75,20 @@ def predict(net: "models.SirenNet", coords: torch.Tensor, batch_size: int) -> to
     return torch.cat([siren_forward(net, coords[lo:lo + batch_size]) for lo in range(0, coords.shape[0], batch_size)])
 
 
+def predict_with_gradient(net: "models.SirenNet", coords: torch.Tensor, batch_size: int):
+    """(y (n, 1), dydx (n, dim_in)): the prediction and its gradient with respect to the coordinates, by plain
+    autograd (the rows of a batch are independent: the gradient of the batch's sum is the per-row gradient)."""
+    ys, gs = [], []
+    for lo in range(0, coords.shape[0], batch_size):
+        x = coords[lo:lo + batch_size].detach().clone().requires_grad_(True)
+        with torch.enable_grad():
+            y = siren_forward(net, x)
+            g, = torch.autograd.grad(y.sum(), x)
+        ys.append(y.detach())
+        gs.append(g.detach())
+    return torch.cat(ys), torch.cat(gs)
+
+
 def psnr(pred: torch.Tensor, truth: torch.Tensor) -> float:
     mse = float(((pred.double() - truth.double()) ** 2).mean())
     return float("inf") if mse == 0 else 10.0 * float(np.log10(1.0 / mse))

@@ -1,0 +1,304 @@
+// Fused SIREN coordinate gradient for gfx950: y and dy/dx of SirenNet(dim_in <= 3 -> H x n -> 1) from ONE walk of
+// the chain, forward mode.
+//
+// With a_l = sin(w_l z_l), z_l = a_{l-1} W_l^T + b_l and the tangent T_l^d = d a_l / d x_d:
+//
+//   T_0^d = w_0 cos(w_0 z_0) (.) W_0[:, d]
+//   T_l^d = (w_l cos(w_l z_l)) (.) (T_{l-1}^d W_l^T)       the product of the value row, on more rows, without bias
+//   dy / dx_d = T_{L-1}^d . w_head
+//
+// so the tile loop of siren_forward_kernel (siren_chain.hip, inference mode) serves as it is when the activation
+// image holds, per POINT, four consecutive rows at a 4-aligned position: the value row and the tangent rows of x_0,
+// x_1, x_2 (rows of absent axes and of points beyond n are zero and are never stored).  The accumulator layout of the
+// 32x32 MFMA (acc_row) puts rows 4 q .. 4 q + 3 of a wave's row block into registers 4 q .. 4 q + 3 of ONE lane: the
+// epilogue, where the tangent rows need the value row's w cos(.), is lane-local -- no shuffles, no LDS traffic --
+// and only one register in four pays a sincos.  The weight chunks (LDS-DMA, double buffered), the bf16x3 products
+// and the split weights are those of the forward kernel (siren_chain.h); nothing (n, H)-sized reaches memory: the
+// call reads n dim_in floats and writes n (1 + dim_in).
+//
+// No atomics and a fixed summation order: two calls on the same input agree bitwise.
+#include <algorithm>
+
+#include "bf16x3.h"
+#include "common.h"
+#include "device_math.h"
+#include "siren_chain.h"
+
+namespace mri {
+namespace {
+
+using namespace chain;
+
+constexpr int kSlots = 4;       // image rows per point: value, d/dx_0, d/dx_1, d/dx_2
+constexpr int kGradMaxIn = 3;   // axes the four slots hold
+constexpr int kGradMaxBlocks = 256;
+
+// Geometry for hidden width H: that of the forward kernel (a wave owns a 32 x CT tile of the layer output, the 8
+// waves are RB row blocks x CB column blocks), the rows counted in points.
+template <int HH>
+struct GradShape {
+  static constexpr int H = HH;
+  static constexpr int CT = H < 64 ? H : 64;
+  static constexpr int NT = CT / 32;
+  static constexpr int CB = H / CT, RB = 8 / CB;
+  static constexpr int rows = 32 * RB;              // image rows of a tile: 64, 128, 256, 256
+  static constexpr int points = rows / kSlots;      // points of a tile: 16, 32, 64, 64
+  static constexpr int ld = H + 4;                  // image row stride: rows 4 banks apart (mod 64)
+  static constexpr int chunks = H / kKc;
+  static constexpr int chunk_bytes = 3 * H * 32;
+  static constexpr int groups = kThreads / H;       // point groups of the first layer's (column, group) mapping
+  static constexpr int ppt = points / groups;       // points per thread there: 8 (4 for H = 32)
+  static_assert(H == 32 || H == 64 || H == 128 || H == 256, "hidden width");
+  static_assert(ppt % 2 == 0 && ppt * groups == points, "first-layer mapping");
+};
+
+template <class S>
+struct GradSmem {
+  char wbuf[2][S::chunk_bytes] __attribute__((aligned(16)));  // weight chunks: term planes [n][2 slots of 8 bf16]
+  float img[S::rows * S::ld];        // the tile's image: point p in rows 4 p .. 4 p + 3
+  float xs[S::points * kSlots];      // coordinates of the tile's points, padded to 4
+  float bias[kMaxSine][S::H];
+  float w_last[S::H];
+};
+
+struct GradArgs {
+  const float* x;                  // (n, dim_in) row-major
+  int64_t n;
+  int dim_in, n_sine;
+  const float* w[kMaxSine + 1];    // [0] (H, dim_in); [1 .. n_sine-1] (H, H); [n_sine] (1, H)
+  const float* b[kMaxSine + 1];
+  float w0_first, w0;
+  float* y;                        // (n)
+  float* dydx;                     // (n, dim_in) row-major
+  const char* wsplit;              // split W of layers 1 .. n_sine-1 (split_matrix_bytes each)
+};
+
+template <class S>
+__global__ __launch_bounds__(kThreads) void siren_gradient_kernel(const GradArgs a) {
+  __shared__ GradSmem<S> sm;
+  constexpr int H = S::H, NT = S::NT;
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int l31 = lane & 31, lh = lane >> 5;
+  const int rb = wave / S::CB, cb = wave % S::CB;
+  const int n_mm = a.n_sine - 1;  // H x H layers
+
+  // ---- small resident parameters ------------------------------------------------------------
+  for (int l = 0; l < a.n_sine; ++l)
+    for (int e = tid; e < H; e += kThreads) sm.bias[l][e] = a.b[l][e];
+  for (int e = tid; e < H; e += kThreads) sm.w_last[e] = a.w[a.n_sine][e];
+  const float b_last = a.b[a.n_sine][0];
+
+  const int64_t tiles = (a.n + S::points - 1) / S::points;
+  const float* a_row = sm.img + (rb * 32 + l31) * S::ld + 4 * lh;
+  const int n0 = cb * S::CT + l31;  // column of tile 0; tile t: + 32 t
+  int boff[NT];
+#pragma unroll
+  for (int t = 0; t < NT; ++t) boff[t] = 32 * (n0 + 32 * t) + 16 * (lh ^ (((n0 + 32 * t) >> 3) & 1));
+
+  // chunk stream: chunk s (layer 1 + (s / chunks) % n_mm) lives in wbuf[s & 1]
+  int s = 0;
+  if (n_mm > 0 && (int64_t)blockIdx.x < tiles) issue_chunk<S>(a.wsplit, 0, sm.wbuf[0], wave, lane);
+
+  for (int64_t tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
+    const int64_t p0 = tile * S::points;  // first point of the tile
+    // ---- coordinates -> LDS ---------------------------------------------------------------------
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    __builtin_amdgcn_s_barrier();  // previous tile is done with img / xs
+    for (int e = tid; e < S::points * kSlots; e += kThreads) {
+      const int p = e / kSlots, d = e % kSlots;
+      sm.xs[e] = (d < a.dim_in && p0 + p < a.n) ? a.x[(p0 + p) * a.dim_in + d] : 0.f;
+    }
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    __builtin_amdgcn_s_barrier();
+    // ---- first layer on the VALU: thread <-> (column, group of points) --------------------------
+    {
+      const int col = tid % H, q0 = (tid / H) * S::ppt;
+      float wr[kGradMaxIn];
+#pragma unroll
+      for (int d = 0; d < kGradMaxIn; ++d) wr[d] = d < a.dim_in ? a.w[0][col * a.dim_in + d] : 0.f;
+      const float bias = sm.bias[0][col];
+#pragma unroll
+      for (int i = 0; i < S::ppt; i += 2) {
+        float z0 = 0.f, z1 = 0.f;
+#pragma unroll
+        for (int d = 0; d < kGradMaxIn; ++d) {
+          if (d < a.dim_in) {
+            z0 += sm.xs[(q0 + i) * kSlots + d] * wr[d];
+            z1 += sm.xs[(q0 + i + 1) * kSlots + d] * wr[d];
+          }
+        }
+        float s0, c0, s1, c1;
+        sincos_fast2(a.w0_first * (z0 + bias), a.w0_first * (z1 + bias), &s0, &c0, &s1, &c1);
+        const bool live0 = p0 + q0 + i < a.n, live1 = p0 + q0 + i + 1 < a.n;
+        const float d0 = a.w0_first * c0, d1 = a.w0_first * c1;
+        float* r0 = sm.img + (q0 + i) * kSlots * S::ld + col;
+        float* r1 = r0 + kSlots * S::ld;
+        r0[0] = live0 ? s0 : 0.f;
+        r1[0] = live1 ? s1 : 0.f;
+#pragma unroll
+        for (int d = 0; d < kGradMaxIn; ++d) {  // (wr[d] = 0 for an absent axis)
+          r0[(1 + d) * S::ld] = live0 ? d0 * wr[d] : 0.f;
+          r1[(1 + d) * S::ld] = live1 ? d1 * wr[d] : 0.f;
+        }
+      }
+    }
+    // ---- H x H layers: the forward kernel's loop ------------------------------------------------
+    for (int l = 1; l <= n_mm; ++l) {
+      f32x16 acc[NT];
+#pragma unroll
+      for (int t = 0; t < NT; ++t)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) acc[t][r] = 0.f;
+      x3::Frag fa;
+#pragma unroll
+      for (int kc = 0; kc < S::chunks; ++kc, ++s) {
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // chunk s has landed (this wave's pieces)
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        __builtin_amdgcn_s_barrier();  // ... for every wave, and wbuf[(s + 1) & 1] is free
+        {
+          const bool more_k = kc + 1 < S::chunks;
+          const int nl = more_k ? l : (l < n_mm ? l + 1 : 1);
+          if (more_k || l < n_mm || tile + gridDim.x < tiles)
+            issue_chunk<S>(a.wsplit + (nl - 1) * split_matrix_bytes(H), more_k ? kc + 1 : 0,
+                           sm.wbuf[(s + 1) & 1], wave, lane);
+        }
+        __builtin_amdgcn_sched_barrier(0);
+        if (kc == 0) fa = first_fragment(a_row);  // (the barrier above completed the image)
+        mma_chunk<NT, H>(acc, fa, kc + 1 < S::chunks ? a_row + (kc + 1) * kKc : nullptr, sm.wbuf[s & 1], boff);
+      }
+      // ---- epilogue: registers 4 q .. 4 q + 3 are one point's value and tangent rows ----------------
+      const float w0 = a.w0;
+      float pa[NT][16];
+#pragma unroll
+      for (int t = 0; t < NT; ++t) {
+        const float bj = sm.bias[l][n0 + 32 * t];
+#pragma unroll
+        for (int q = 0; q < 4; q += 2) {
+          float s0, c0, s1, c1;
+          sincos_fast2(w0 * (acc[t][4 * q] + bj), w0 * (acc[t][4 * q + 4] + bj), &s0, &c0, &s1, &c1);
+          const float d0 = w0 * c0, d1 = w0 * c1;
+          pa[t][4 * q] = s0, pa[t][4 * q + 4] = s1;
+#pragma unroll
+          for (int j = 1; j < kSlots; ++j) {
+            pa[t][4 * q + j] = d0 * acc[t][4 * q + j];
+            pa[t][4 * q + 4 + j] = d1 * acc[t][4 * q + 4 + j];
+          }
+        }
+      }
+      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+      __builtin_amdgcn_s_barrier();  // every wave has read the image for the last time
+#pragma unroll
+      for (int t = 0; t < NT; ++t)
+#pragma unroll
+        for (int r = 0; r < 16; ++r)
+          sm.img[(rb * 32 + acc_row(r, lh)) * S::ld + n0 + t * 32] = pa[t][r];
+    }
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    __builtin_amdgcn_s_barrier();  // image complete
+    // ---- head: image row . w_head, one wave per row; slot 0 -> y (+ bias), slot 1 + d -> dydx[:, d] ----
+    {
+      constexpr int kPer = H >= 64 ? H / 64 : 1;  // elements per lane (H = 32: half the lanes)
+      float wv[kPer];
+#pragma unroll
+      for (int j = 0; j < kPer; ++j) wv[j] = lane + 64 * j < H ? sm.w_last[lane + 64 * j] : 0.f;
+#pragma unroll 4
+      for (int i = 0; i < S::rows / 8; ++i) {
+        const int row = wave * (S::rows / 8) + i;  // wave-uniform
+        const int slot = row % kSlots;
+        const int64_t p = p0 + row / kSlots;
+        if (slot > a.dim_in || p >= a.n) continue;
+        float acc1 = 0.f;
+#pragma unroll
+        for (int j = 0; j < kPer; ++j)
+          if (lane + 64 * j < H) acc1 += sm.img[row * S::ld + lane + 64 * j] * wv[j];
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) acc1 += __shfl_down(acc1, off, 64);
+        if (lane == 0) {
+          if (slot == 0)
+            a.y[p] = acc1 + b_last;
+          else
+            a.dydx[p * a.dim_in + (slot - 1)] = acc1;
+        }
+      }
+    }
+  }
+}
+
+bool gradient_supported(int dim_in, int hidden, int n_sine, int dim_out) {
+  return (hidden == 32 || hidden == 64 || hidden == 128 || hidden == 256) && dim_in >= 1 &&
+         dim_in <= kGradMaxIn && n_sine >= 1 && n_sine <= kMaxSine && dim_out == 1;
+}
+
+int64_t gradient_split_bytes(int hidden, int n_sine) {
+  return n_sine > 1 ? (n_sine - 1) * split_matrix_bytes(hidden) : 0;
+}
+
+template <int H>
+int launch_gradient(const GradArgs& a, hipStream_t st) {
+  using S = GradShape<H>;
+  const int blocks = (int)std::min<int64_t>(ceil_div(a.n, S::points), kGradMaxBlocks);  // one workgroup per CU
+  hipLaunchKernelGGL((siren_gradient_kernel<S>), dim3(blocks), dim3(kThreads), 0, st, a);
+  return check_launch("siren_gradient_kernel");
+}
+
+}  // namespace
+}  // namespace mri
+
+using namespace mri;
+
+extern "C" int mri_siren_gradient_supported(int32_t dim_in, int32_t hidden, int32_t n_sine_layers,
+                                            int32_t dim_out) {
+  return gradient_supported(dim_in, hidden, n_sine_layers, dim_out) ? 1 : 0;
+}
+
+extern "C" int64_t mri_siren_gradient_workspace_bytes(int32_t hidden, int32_t n_sine_layers) {
+  if (!gradient_supported(1, hidden, n_sine_layers, 1)) return -1;
+  return gradient_split_bytes(hidden, n_sine_layers);
+}
+
+extern "C" int mri_siren_gradient(const float* x, int64_t n, int32_t dim_in, int32_t hidden,
+                                  int32_t n_sine_layers, const float* const* weight,
+                                  const float* const* bias, float w0_first, float w0, float* y, float* dydx,
+                                  void* workspace, int64_t workspace_bytes, void* stream) {
+  MRI_REQUIRE(hidden == 32 || hidden == 64 || hidden == 128 || hidden == 256,
+              "SIREN gradient: hidden = %d is not supported (32 / 64 / 128 / 256)", hidden);
+  MRI_REQUIRE(dim_in >= 1 && dim_in <= kGradMaxIn, "SIREN gradient: dim_in = %d is not supported (1 .. %d)", dim_in,
+              kGradMaxIn);
+  MRI_REQUIRE(n_sine_layers >= 1 && n_sine_layers <= kMaxSine,
+              "SIREN gradient: n_sine_layers = %d is not supported (1 .. %d)", n_sine_layers, kMaxSine);
+  MRI_REQUIRE(n >= 0 && n < (1ll << 31), "n = %lld out of range", (long long)n);
+  if (n == 0) return MRI_OK;
+  MRI_REQUIRE(x, "x is NULL");
+  MRI_REQUIRE(weight, "weight is NULL");
+  MRI_REQUIRE(bias, "bias is NULL");
+  MRI_REQUIRE(y, "y is NULL");
+  MRI_REQUIRE(dydx, "dydx is NULL");
+  MRI_REQUIRE((reinterpret_cast<uintptr_t>(x) & 3) == 0, "x must be 4-byte aligned");
+  MRI_REQUIRE((reinterpret_cast<uintptr_t>(y) & 3) == 0, "y must be 4-byte aligned");
+  MRI_REQUIRE((reinterpret_cast<uintptr_t>(dydx) & 3) == 0, "dydx must be 4-byte aligned");
+  const int64_t need = gradient_split_bytes(hidden, n_sine_layers);
+  MRI_REQUIRE(need == 0 || (workspace && workspace_bytes >= need && (reinterpret_cast<uintptr_t>(workspace) & 15) == 0),
+              "workspace: the SIREN gradient needs %lld bytes, 16-byte aligned (mri_siren_gradient_workspace_bytes)",
+              (long long)need);
+  GradArgs a{};
+  a.x = x, a.n = n, a.dim_in = dim_in, a.n_sine = n_sine_layers;
+  a.w0_first = w0_first, a.w0 = w0, a.y = y, a.dydx = dydx;
+  for (int l = 0; l <= n_sine_layers; ++l) {
+    MRI_REQUIRE(weight[l], "weight[%d] is NULL", l);
+    MRI_REQUIRE(bias[l], "bias[%d] is NULL", l);
+    MRI_REQUIRE((reinterpret_cast<uintptr_t>(weight[l]) & 15) == 0, "weight[%d] must be 16-byte aligned", l);
+    a.w[l] = weight[l], a.b[l] = bias[l];
+  }
+  a.wsplit = static_cast<const char*>(workspace);
+  hipStream_t st = (hipStream_t)stream;
+  if (int rc = split_weights_ld(weight + 1, n_sine_layers - 1, hidden, hidden, false, static_cast<char*>(workspace),
+                                split_matrix_bytes(hidden), st))
+    return rc;
+  switch (hidden) {
+    case 32: return launch_gradient<32>(a, st);
+    case 64: return launch_gradient<64>(a, st);
+    case 128: return launch_gradient<128>(a, st);
+    default: return launch_gradient<256>(a, st);
+  }
+}

@@ -145,6 +145,20 @@ class BaseMLP(_Base):
         x, y = batch
         return self(x)
 
+    def forward_with_gradient(self, x) -> Tuple[torch.Tensor, torch.Tensor]:
+        """(y (n, 1), dydx (n, dim_in)), both detached: the prediction and its gradient with respect to the
+        coordinates, dydx[i, d] = dy[i] / dx[i, d].  The generic body: autograd through the model's own `forward`
+        (every op returns the gradient of its input; HashMLP through the hash grid's input backward).  The
+        parameters gain no `.grad`."""
+        if self.dim_out != 1:
+            raise ValueError(f"forward_with_gradient needs dim_out == 1 (got {self.dim_out}): the gradient of one "
+                             "output with respect to the coordinates")
+        with torch.enable_grad():
+            xg = x.detach().clone().requires_grad_(True)
+            y = self.forward(xg)
+            dydx, = torch.autograd.grad(y.sum(), xg)
+        return y.detach(), dydx.detach()
+
     def set_parameters(self, theta):
         """Copy a sequence of tensors into the parameters, in state-dict order
         (reference models.py:87-96)."""
@@ -221,6 +235,39 @@ class SirenNet(BaseMLP):
             x = layer(x)
         return self.last_layer(x)
 
+    def _gradient_plan(self, x):
+        """Arguments of the fused gradient kernel (csrc/siren_gradient.hip), or None where the generic body serves:
+        the plain chain only -- sine layers with one w0 behind the first, an identity head, biases everywhere, a
+        shape the kernel takes -- and a tensor on the GPU."""
+        ls = list(self.layers) + [self.last_layer]
+        if not x.is_cuda or x.dtype != torch.float32 or x.dim() != 2 or any(l.bias is None for l in ls):
+            return None
+        if any(not isinstance(l.activation, Sine) for l in ls[:-1]) or not isinstance(ls[-1].activation, nn.Identity):
+            return None
+        if len({float(l.activation.w0) for l in ls[1:-1]}) > 1:
+            return None
+        hidden, dim_in = ls[0].weight.shape
+        if x.shape[1] != dim_in or any(l.weight.shape != (hidden, hidden) for l in ls[1:-1]) \
+                or ls[-1].weight.shape != (1, hidden):
+            return None
+        if not ops.siren_gradient_supported(dim_in, hidden, len(ls) - 1, self.dim_out):
+            return None
+        w0_first = float(ls[0].activation.w0)
+        return dict(weights=[l.weight.detach() for l in ls], biases=[l.bias.detach() for l in ls],
+                    w0_first=w0_first, w0=float(ls[1].activation.w0) if len(ls) > 2 else w0_first)
+
+    def forward_with_gradient(self, x) -> Tuple[torch.Tensor, torch.Tensor]:
+        """As BaseMLP.forward_with_gradient; the plain chain on the GPU runs ONE kernel that carries the value and
+        the tangents of a point through the layers together (ops.siren_gradient), everything else the generic
+        body."""
+        if self.dim_out != 1:
+            raise ValueError(f"forward_with_gradient needs dim_out == 1 (got {self.dim_out})")
+        plan = self._gradient_plan(x)
+        if plan is None:
+            return super().forward_with_gradient(x)
+        with torch.no_grad():
+            return ops.siren_gradient(x.detach(), plan["weights"], plan["biases"], plan["w0_first"], plan["w0"])
+
 
 def cast_tuple(val, repeat=1):
     return val if isinstance(val, tuple) else ((val,) * repeat)
@@ -281,6 +328,11 @@ class ModulatedSirenNet(SirenNet):
         for layer, mod in zip(self.siren.layers, mods):
             x = ops.modulate(layer(x), mod)
         return self.siren.last_layer(x)
+
+    def forward_with_gradient(self, x) -> Tuple[torch.Tensor, torch.Tensor]:
+        """The generic body (autograd through THIS forward): the plain-chain kernel SirenNet dispatches to computes
+        another network."""
+        return BaseMLP.forward_with_gradient(self, x)
 
 
 class HashMLP(BaseMLP):

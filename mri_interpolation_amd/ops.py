@@ -688,6 +688,33 @@ def _siren_scratch(device, n, hidden, n_sine):
     return ws
 
 
+def siren_gradient_supported(dim_in: int, hidden: int, n_sine_layers: int, dim_out: int) -> bool:
+    return bool(_lib.load().mri_siren_gradient_supported(dim_in, hidden, n_sine_layers, dim_out))
+
+
+def siren_gradient(x, weights, biases, w0_first: float, w0: float, y=None, dydx=None):
+    """(y (n, 1), dydx (n, dim_in)) = SirenNet(x) and its gradient with respect to x, dydx[i, d] = dy[i] / dx[i, d],
+    in one persistent kernel (csrc/siren_gradient.hip): the value and the dim_in <= 3 tangents of a point travel the
+    chain together, nothing (n, hidden)-sized is written.  weights / biases: the sine layers' then the head's."""
+    _gpu(x, y, dydx, *weights, *biases)
+    x = _rowmajor(x).contiguous()
+    n, dim_in = x.shape
+    n_sine, hidden = len(weights) - 1, weights[0].shape[0]
+    if y is None:
+        y = torch.empty((n, 1), device=x.device, dtype=torch.float32)
+    if dydx is None:
+        dydx = torch.empty((n, dim_in), device=x.device, dtype=torch.float32)
+    if y.numel() != n or dydx.shape != (n, dim_in):
+        raise ValueError("siren_gradient: y holds n values, dydx is (n, dim_in)")
+    for t in list(weights) + list(biases) + [y, dydx]:
+        if not t.is_contiguous():
+            raise ValueError("siren_gradient needs contiguous parameters and buffers")
+    ws = _siren_scratch(x.device, max(n, 1), hidden, n_sine)  # holds the split weights
+    _lib.call("mri_siren_gradient", _ptr(x), n, dim_in, hidden, n_sine, _ptr_array(weights), _ptr_array(biases),
+              float(w0_first), float(w0), _ptr(y), _ptr(dydx), _ptr(ws), ws.numel() * 4, _stream())
+    return y, dydx
+
+
 def _opt_ptr_array(tensors):
     return (C.c_void_p * len(tensors))(*[t.data_ptr() if t is not None else None for t in tensors])
 

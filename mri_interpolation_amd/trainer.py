@@ -28,7 +28,7 @@ import contextlib
 import ctypes as C
 import os
 import time
-from typing import Dict, List, Optional
+from typing import Dict, List, Optional, Tuple
 
 import torch
 
@@ -1517,6 +1517,20 @@ class Trainer:
             else:
                 out.append(model.predict_step((x, y), batch_idx))
         return out
+
+    def predict_with_gradient(self, model, dataloaders) -> Tuple[List[torch.Tensor], List[torch.Tensor]]:
+        """(per-batch predictions (n, 1), per-batch gradients (n, dim_in) with respect to the coordinates): the
+        twin of `predict` through `model.forward_with_gradient` (SirenNet / PsfSirenNet: one fused kernel per
+        batch; every other model: autograd through its forward)."""
+        if next(model.parameters()).device.type != "cuda":
+            model.cuda()
+        model.eval()
+        ys, grads = [], []
+        for x, _ in dataloaders:
+            y, g = model.forward_with_gradient(x)
+            ys.append(y)
+            grads.append(g)
+        return ys, grads
 
 
 def level_group_ranges(sizes, groups: int):
