@@ -474,10 +474,12 @@ int mri_siren_forward_loss(const float* x, const float* target, int64_t n, int64
  * the tangent of sine layer l is w_l cos(w_l z_l) (.) (tangent of layer l - 1) W_l^T, the value row's product on
  * more rows --, so a point travels as four consecutive rows of the LDS activation image (value, d/dx_0, d/dx_1,
  * d/dx_2) through the tile loop of mri_siren_forward's inference kernel; the hidden x hidden products run on the
- * same bf16x3 form.  Nothing (n, hidden)-sized is written: the call reads n dim_in floats and writes n (1 + dim_in).
+ * same bf16x3 form.  dim_in = 4 takes the eight-row form of the same kernel (value, d/dx_0, d/dx_1, d/dx_2 | value,
+ * d/dx_3, 0, 0: the value row twice, so that each half of a point meets its own w cos(.) in one lane).
+ * Nothing (n, hidden)-sized is written: the call reads n dim_in floats and writes n (1 + dim_in).
  * No atomics, a fixed summation order: bitwise reproducible.  At most 256 workgroups walk the tiles of 1024 / hidden
- * points (64 at hidden 32).
- * Supported (mri_siren_gradient_supported is the truth): hidden in {32, 64, 128, 256}, 1 <= dim_in <= 3,
+ * points (64 at hidden 32); half as many points per tile with dim_in = 4.
+ * Supported (mri_siren_gradient_supported is the truth): hidden in {32, 64, 128, 256}, 1 <= dim_in <= 4,
  * 1 <= n_sine_layers <= MRI_SIREN_MAX_LAYERS, dim_out = 1; anything else is refused with MRI_ERR_INVALID_ARGUMENT,
  * the offending argument named in mri_last_error.  n = 0 returns 0 without a launch.
  * weight / bias: as mri_siren_forward (weight[l] 16-byte aligned); x, y and dydx are accessed 4 bytes at a time at

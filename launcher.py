@@ -79,7 +79,9 @@ def parse_args(argv=None):
     p.add_argument("--save_gradient", action="store_true",
                    help="after pred.nii.gz also write gradient.nii.gz, float32 of shape image_shape + (dim_in,): the "
                         "change of the network's output per voxel step along each axis (models with one output; "
-                        "SirenNet / PsfSirenNet through the fused gradient kernel, the others through autograd)")
+                        "SirenNet / PsfSirenNet through the fused gradient kernel, a 4-D volume's temporal derivative "
+                        "included, the others through autograd), and for every interpolation{shape}.nii.gz a "
+                        "gradient_interpolation{shape}.nii.gz of shape + (dim_in,) in voxel steps of THAT grid")
     p.add_argument("--out_dir", type=str, default=None)
     p.add_argument("--max_steps", type=int, default=-1)
     p.add_argument("--log_every", type=int, default=50)
@@ -112,13 +114,16 @@ def check_save_gradient(model_cls, dim_out):
                          "volume holds the derivative of ONE value per axis")
 
 
-def save_gradient_volume(dydx, config, out_dir, nifti):
-    """gradient.nii.gz: dydx (N, dim_in) in grid order -> image_shape + (dim_in,), in output units per voxel step."""
+def save_gradient_volume(dydx, config, out_dir, nifti, shape=None, name="gradient.nii.gz"):
+    """gradient.nii.gz: dydx (N, dim_in) in grid order -> image_shape + (dim_in,), in output units per voxel step.
+    With `shape` and `name`: the same on another grid of the volume (gradient_interpolation{shape}.nii.gz), in
+    voxel steps of that grid."""
     import numpy as np
-    scale = np.asarray(gradient_voxel_scale(config.image_shape, config.norm_siren), dtype=np.float32)
+    shape = tuple(config.image_shape if shape is None else shape)
+    scale = np.asarray(gradient_voxel_scale(shape, config.norm_siren), dtype=np.float32)
     grad = np.asarray(dydx.detach().cpu().numpy(), dtype=np.float32) * scale
-    grad = np.ascontiguousarray(grad.reshape(tuple(config.image_shape) + (config.dim_in,)), dtype=np.float32)
-    nifti.save(grad, os.path.join(out_dir, "gradient.nii.gz"))
+    grad = np.ascontiguousarray(grad.reshape(shape + (config.dim_in,)), dtype=np.float32)
+    nifti.save(grad, os.path.join(out_dir, name))
     return grad
 
 
@@ -303,6 +308,10 @@ def main(argv=None):
         interp = torch.concat(trainer.predict(model, loader))
         interp_im = np.array(interp.reshape(shape).detach().cpu().numpy(), dtype=np.float32)
         nifti.save(interp_im, os.path.join(out_dir, f"interpolation{tuple(shape)}.nii.gz"))
+        if args.save_gradient:
+            _, grads = trainer.predict_with_gradient(model, loader)
+            save_gradient_volume(torch.concat(grads), config, out_dir, nifti, shape=shape,
+                                 name=f"gradient_interpolation{tuple(shape)}.nii.gz")
 
     if args.holdout_odd_frames:
         odd = datamodules.MriImage(volume=volume, norm_siren=config.norm_siren,
@@ -357,9 +366,13 @@ def main_cpu(args, config, volume):
         if len(shape) != config.dim_in:
             print(f"skip interpolation shape {shape}: volume is {config.dim_in}-D")
             continue
-        interp = cpu_path.predict(model, cpu_path.grid_coords(shape, norm_siren=True), config.batch_size)
+        grid = cpu_path.grid_coords(shape, norm_siren=True)
+        interp = cpu_path.predict(model, grid, config.batch_size)
         nifti.save(np.array(interp.reshape(shape).numpy(), dtype=np.float32),
                    os.path.join(out_dir, f"interpolation{tuple(shape)}.nii.gz"))
+        if args.save_gradient:
+            save_gradient_volume(cpu_path.predict_with_gradient(model, grid, config.batch_size)[1], config, out_dir, nifti,
+                                 shape=shape, name=f"gradient_interpolation{tuple(shape)}.nii.gz")
     config.train_seconds, config.psnr_db, config.accelerator = train_seconds, quality, "cpu"
     config.coords_per_second = steps * config.batch_size / max(train_seconds, 1e-9)
     config.final_loss = losses[-1] if losses else None

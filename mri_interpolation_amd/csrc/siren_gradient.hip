@@ -1,4 +1,4 @@
-// Fused SIREN coordinate gradient for gfx950: y and dy/dx of SirenNet(dim_in <= 3 -> H x n -> 1) from ONE walk of
+// Fused SIREN coordinate gradient for gfx950: y and dy/dx of SirenNet(dim_in <= 4 -> H x n -> 1) from ONE walk of
 // the chain, forward mode.
 //
 // With a_l = sin(w_l z_l), z_l = a_{l-1} W_l^T + b_l and the tangent T_l^d = d a_l / d x_d:
@@ -16,6 +16,15 @@
 // and the split weights are those of the forward kernel (siren_chain.h); nothing (n, H)-sized reaches memory: the
 // call reads n dim_in floats and writes n (1 + dim_in).
 //
+// dim_in = 4 (a dynamic sequence: x, y, z, t) takes the EIGHT-slot instantiation of the same kernel body: a point's
+// rows sit at an 8-aligned position in the order [value, d/dx_0, d/dx_1, d/dx_2 | value, d/dx_3, 0, 0].  acc_row puts
+// rows 8 q .. 8 q + 3 into registers 4 q .. 4 q + 3 of lane l31 and rows 8 q + 4 .. 8 q + 7 into the same registers of
+// lane l31 + 32, so with the value row written TWICE by the first layer (the rows of an MFMA are independent: the
+// copy in slot 4 stays identical to slot 0 through every layer) register 4 q is a value row and 4 q + 1 .. 4 q + 3
+// are its tangents in BOTH lane halves: the epilogue is the four-slot form's expression, still lane-local, and the
+// copy's sincos runs in the instructions the wave issues anyway.  A tile holds half the points (8 / 16 / 32 / 32);
+// the image, its stride and the weight stream are unchanged.  The head skips slots 4, 6 and 7.
+//
 // No atomics and a fixed summation order: two calls on the same input agree bitwise.
 #include <algorithm>
 
@@ -29,25 +38,28 @@ namespace {
 
 using namespace chain;
 
-constexpr int kSlots = 4;       // image rows per point: value, d/dx_0, d/dx_1, d/dx_2
-constexpr int kGradMaxIn = 3;   // axes the four slots hold
+constexpr int kGradMaxIn = 4;   // axes the eight-slot form holds (the four-slot form: 3)
 constexpr int kGradMaxBlocks = 256;
 
 // Geometry for hidden width H: that of the forward kernel (a wave owns a 32 x CT tile of the layer output, the 8
-// waves are RB row blocks x CB column blocks), the rows counted in points.
-template <int HH>
+// waves are RB row blocks x CB column blocks), the rows counted in points of SL image rows: 4 (value, d/dx_0,
+// d/dx_1, d/dx_2) for dim_in <= 3, 8 (value, d/dx_0 .. d/dx_2 | value, d/dx_3, 0, 0) for dim_in = 4.
+template <int HH, int SL>
 struct GradShape {
   static constexpr int H = HH;
+  static constexpr int slots = SL;
+  static constexpr int max_in = SL == 4 ? 3 : 4;    // axes the slots hold
   static constexpr int CT = H < 64 ? H : 64;
   static constexpr int NT = CT / 32;
   static constexpr int CB = H / CT, RB = 8 / CB;
   static constexpr int rows = 32 * RB;              // image rows of a tile: 64, 128, 256, 256
-  static constexpr int points = rows / kSlots;      // points of a tile: 16, 32, 64, 64
+  static constexpr int points = rows / SL;          // points of a tile: 16, 32, 64, 64 (8 slots: 8, 16, 32, 32)
   static constexpr int ld = H + 4;                  // image row stride: rows 4 banks apart (mod 64)
   static constexpr int chunks = H / kKc;
   static constexpr int chunk_bytes = 3 * H * 32;
   static constexpr int groups = kThreads / H;       // point groups of the first layer's (column, group) mapping
-  static constexpr int ppt = points / groups;       // points per thread there: 8 (4 for H = 32)
+  static constexpr int ppt = points / groups;       // points per thread there: 8, 8, 8, 4 (8 slots: 4, 4, 4, 2)
+  static_assert(SL == 4 || SL == 8, "image rows per point");
   static_assert(H == 32 || H == 64 || H == 128 || H == 256, "hidden width");
   static_assert(ppt % 2 == 0 && ppt * groups == points, "first-layer mapping");
 };
@@ -55,8 +67,8 @@ struct GradShape {
 template <class S>
 struct GradSmem {
   char wbuf[2][S::chunk_bytes] __attribute__((aligned(16)));  // weight chunks: term planes [n][2 slots of 8 bf16]
-  float img[S::rows * S::ld];        // the tile's image: point p in rows 4 p .. 4 p + 3
-  float xs[S::points * kSlots];      // coordinates of the tile's points, padded to 4
+  float img[S::rows * S::ld];        // the tile's image: point p in rows slots p .. slots p + slots - 1
+  float xs[S::points * S::slots];    // coordinates of the tile's points, padded to slots
   float bias[kMaxSine][S::H];
   float w_last[S::H];
 };
@@ -76,7 +88,7 @@ struct GradArgs {
 template <class S>
 __global__ __launch_bounds__(kThreads) void siren_gradient_kernel(const GradArgs a) {
   __shared__ GradSmem<S> sm;
-  constexpr int H = S::H, NT = S::NT;
+  constexpr int H = S::H, NT = S::NT, kSlots = S::slots, kMaxIn = S::max_in;
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int l31 = lane & 31, lh = lane >> 5;
@@ -114,15 +126,15 @@ __global__ __launch_bounds__(kThreads) void siren_gradient_kernel(const GradArgs
     // ---- first layer on the VALU: thread <-> (column, group of points) --------------------------
     {
       const int col = tid % H, q0 = (tid / H) * S::ppt;
-      float wr[kGradMaxIn];
+      float wr[kMaxIn];
 #pragma unroll
-      for (int d = 0; d < kGradMaxIn; ++d) wr[d] = d < a.dim_in ? a.w[0][col * a.dim_in + d] : 0.f;
+      for (int d = 0; d < kMaxIn; ++d) wr[d] = d < a.dim_in ? a.w[0][col * a.dim_in + d] : 0.f;
       const float bias = sm.bias[0][col];
 #pragma unroll
       for (int i = 0; i < S::ppt; i += 2) {
         float z0 = 0.f, z1 = 0.f;
 #pragma unroll
-        for (int d = 0; d < kGradMaxIn; ++d) {
+        for (int d = 0; d < kMaxIn; ++d) {
           if (d < a.dim_in) {
             z0 += sm.xs[(q0 + i) * kSlots + d] * wr[d];
             z1 += sm.xs[(q0 + i + 1) * kSlots + d] * wr[d];
@@ -137,9 +149,17 @@ __global__ __launch_bounds__(kThreads) void siren_gradient_kernel(const GradArgs
         r0[0] = live0 ? s0 : 0.f;
         r1[0] = live1 ? s1 : 0.f;
 #pragma unroll
-        for (int d = 0; d < kGradMaxIn; ++d) {  // (wr[d] = 0 for an absent axis)
+        for (int d = 0; d < 3; ++d) {  // (wr[d] = 0 for an absent axis)
           r0[(1 + d) * S::ld] = live0 ? d0 * wr[d] : 0.f;
           r1[(1 + d) * S::ld] = live1 ? d1 * wr[d] : 0.f;
+        }
+        if constexpr (kSlots == 8) {  // upper lane half of the accumulator: the value row again, d/dx_3, two zero rows
+          r0[4 * S::ld] = live0 ? s0 : 0.f;
+          r1[4 * S::ld] = live1 ? s1 : 0.f;
+          r0[5 * S::ld] = live0 ? d0 * wr[3] : 0.f;
+          r1[5 * S::ld] = live1 ? d1 * wr[3] : 0.f;
+          r0[6 * S::ld] = r0[7 * S::ld] = 0.f;
+          r1[6 * S::ld] = r1[7 * S::ld] = 0.f;
         }
       }
     }
@@ -167,7 +187,8 @@ __global__ __launch_bounds__(kThreads) void siren_gradient_kernel(const GradArgs
         if (kc == 0) fa = first_fragment(a_row);  // (the barrier above completed the image)
         mma_chunk<NT, H>(acc, fa, kc + 1 < S::chunks ? a_row + (kc + 1) * kKc : nullptr, sm.wbuf[s & 1], boff);
       }
-      // ---- epilogue: registers 4 q .. 4 q + 3 are one point's value and tangent rows ----------------
+      // ---- epilogue: registers 4 q .. 4 q + 3 are one point's value and tangent rows (8 slots: of either half
+      //      of the point, the value row being there twice) -----------------------------------------------
       const float w0 = a.w0;
       float pa[NT][16];
 #pragma unroll
@@ -180,7 +201,7 @@ __global__ __launch_bounds__(kThreads) void siren_gradient_kernel(const GradArgs
           const float d0 = w0 * c0, d1 = w0 * c1;
           pa[t][4 * q] = s0, pa[t][4 * q + 4] = s1;
 #pragma unroll
-          for (int j = 1; j < kSlots; ++j) {
+          for (int j = 1; j < 4; ++j) {
             pa[t][4 * q + j] = d0 * acc[t][4 * q + j];
             pa[t][4 * q + 4 + j] = d1 * acc[t][4 * q + 4 + j];
           }
@@ -196,7 +217,8 @@ __global__ __launch_bounds__(kThreads) void siren_gradient_kernel(const GradArgs
     }
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();  // image complete
-    // ---- head: image row . w_head, one wave per row; slot 0 -> y (+ bias), slot 1 + d -> dydx[:, d] ----
+    // ---- head: image row . w_head, one wave per row; slot 0 -> y (+ bias), slot 1 + d -> dydx[:, d]; of the
+    //      upper four of 8 slots only slot 5 -> dydx[:, 3] is stored ------------------------------------------
     {
       constexpr int kPer = H >= 64 ? H / 64 : 1;  // elements per lane (H = 32: half the lanes)
       float wv[kPer];
@@ -207,7 +229,8 @@ __global__ __launch_bounds__(kThreads) void siren_gradient_kernel(const GradArgs
         const int row = wave * (S::rows / 8) + i;  // wave-uniform
         const int slot = row % kSlots;
         const int64_t p = p0 + row / kSlots;
-        if (slot > a.dim_in || p >= a.n) continue;
+        const int axis = slot < 4 ? slot - 1 : (slot == 5 ? 3 : kMaxIn);  // wave-uniform; -1: the value
+        if (axis >= a.dim_in || p >= a.n) continue;
         float acc1 = 0.f;
 #pragma unroll
         for (int j = 0; j < kPer; ++j)
@@ -218,13 +241,14 @@ __global__ __launch_bounds__(kThreads) void siren_gradient_kernel(const GradArgs
           if (slot == 0)
             a.y[p] = acc1 + b_last;
           else
-            a.dydx[p * a.dim_in + (slot - 1)] = acc1;
+            a.dydx[p * a.dim_in + axis] = acc1;
         }
       }
     }
   }
 }
 
+// dim_in = 4 is served by the eight-slot form for exactly the cases of the four-slot form.
 bool gradient_supported(int dim_in, int hidden, int n_sine, int dim_out) {
   return (hidden == 32 || hidden == 64 || hidden == 128 || hidden == 256) && dim_in >= 1 &&
          dim_in <= kGradMaxIn && n_sine >= 1 && n_sine <= kMaxSine && dim_out == 1;
@@ -234,12 +258,17 @@ int64_t gradient_split_bytes(int hidden, int n_sine) {
   return n_sine > 1 ? (n_sine - 1) * split_matrix_bytes(hidden) : 0;
 }
 
-template <int H>
-int launch_gradient(const GradArgs& a, hipStream_t st) {
-  using S = GradShape<H>;
+template <int H, int SL>
+int launch_slots(const GradArgs& a, hipStream_t st) {
+  using S = GradShape<H, SL>;
   const int blocks = (int)std::min<int64_t>(ceil_div(a.n, S::points), kGradMaxBlocks);  // one workgroup per CU
   hipLaunchKernelGGL((siren_gradient_kernel<S>), dim3(blocks), dim3(kThreads), 0, st, a);
   return check_launch("siren_gradient_kernel");
+}
+
+template <int H>
+int launch_gradient(const GradArgs& a, hipStream_t st) {
+  return a.dim_in <= 3 ? launch_slots<H, 4>(a, st) : launch_slots<H, 8>(a, st);
 }
 
 }  // namespace

@@ -694,8 +694,9 @@ def siren_gradient_supported(dim_in: int, hidden: int, n_sine_layers: int, dim_o
 
 def siren_gradient(x, weights, biases, w0_first: float, w0: float, y=None, dydx=None):
     """(y (n, 1), dydx (n, dim_in)) = SirenNet(x) and its gradient with respect to x, dydx[i, d] = dy[i] / dx[i, d],
-    in one persistent kernel (csrc/siren_gradient.hip): the value and the dim_in <= 3 tangents of a point travel the
-    chain together, nothing (n, hidden)-sized is written.  weights / biases: the sine layers' then the head's."""
+    in one persistent kernel (csrc/siren_gradient.hip): the value and the dim_in <= 4 tangents of a point travel the
+    chain together (four image rows per point for dim_in <= 3, eight for dim_in = 4: a 4-D volume, time among the
+    axes), nothing (n, hidden)-sized is written.  weights / biases: the sine layers' then the head's."""
     _gpu(x, y, dydx, *weights, *biases)
     x = _rowmajor(x).contiguous()
     n, dim_in = x.shape

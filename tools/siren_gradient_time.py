@@ -10,11 +10,13 @@
 (c0) forward_lds  the same with the "siren_rows" option at 0: the LDS-image forward kernel, the form the gradient
                   kernel shares its tile loop with (the like-for-like ratio).
 
-Two networks: BASELINE config 3's (3 -> 256 x 5 -> 1) and 3 -> 64 x 4 -> 1.  All legs run in one process on the same
-seeded rows; after a warm-up of every form the legs alternate and each number is the median over the legs of a leg's
-mean call time (HIP events around `calls` calls, synchronised).  The cost model: four image rows per point through
-the H x H products and one sincos per four rows, so (a) should stay under 4 x (c0).  Kernel launches per call are
-counted with the profiler.  Writes DIR/siren_gradient_<hidden>x<layers>_n<rows>.json."""
+Four networks: BASELINE config 3's (3 -> 256 x 5 -> 1) and 3 -> 64 x 4 -> 1, and for a 4-D volume (the kernel's
+eight-slot form) 4 -> 256 x 5 -> 1 and 4 -> 128 x 6 -> 1, the width and depth the launcher's SirenNet defaults to.
+All legs run in one process on the same seeded rows; after a warm-up of every form the legs alternate and each
+number is the median over the legs of a leg's mean call time (HIP events around `calls` calls, synchronised).  The
+cost model: four image rows per point (eight with dim_in = 4) through the H x H products and one sincos per four
+rows, so (a) should stay under 4 x (c0) (8 x with dim_in = 4).  Kernel launches per call are counted with the
+profiler.  Writes DIR/siren_gradient_<hidden>x<layers>_n<rows>.json (siren_gradient_d4_... for dim_in = 4)."""
 import json
 import os
 import statistics
@@ -27,7 +29,19 @@ import torch  # noqa: E402
 
 from mri_interpolation_amd import _lib, models, ops  # noqa: E402
 
-NETS = [dict(dim_in=3, dim_hidden=256, dim_out=1, n_layers=5), dict(dim_in=3, dim_hidden=64, dim_out=1, n_layers=4)]
+NETS = [dict(dim_in=3, dim_hidden=256, dim_out=1, n_layers=5), dict(dim_in=3, dim_hidden=64, dim_out=1, n_layers=4),
+        dict(dim_in=4, dim_hidden=256, dim_out=1, n_layers=5), dict(dim_in=4, dim_hidden=128, dim_out=1, n_layers=6)]
+
+
+def slots(dim_in):
+    """Image rows per point of the gradient kernel."""
+    return 4 if dim_in <= 3 else 8
+
+
+def profile_name(config, n):
+    """The 3-D networks keep the names of the committed profiles; other input dimensions carry theirs."""
+    dim = "" if config["dim_in"] == 3 else f"d{config['dim_in']}_"
+    return f"siren_gradient_{dim}{config['dim_hidden']}x{config['n_layers']}_n{n}.json"
 
 
 def leg_ms(fn, calls):
@@ -98,7 +112,7 @@ def measure(config, n, warmup=3, calls=5, legs=7):
     res["kernel_vs_autograd"] = dict(gain_ms=t["autograd"] - t["kernel"], largest_spread_ms=spread,
                                      ratio=t["kernel"] / t["autograd"], beyond_spread=t["autograd"] - t["kernel"] > spread)
     res["kernel_over_forward"] = dict(default=t["kernel"] / t["forward"], lds_form=t["kernel"] / t["forward_lds"],
-                                      cost_model_bound=4.0)
+                                      cost_model_bound=float(slots(config["dim_in"])))
     res["ns_per_point"] = {k: v * 1e6 / n for k, v in t.items()}
     res["launches_per_call"] = {k: launches(fn) for k, fn in forms.items()}
     res["bytes_per_call"] = dict(kernel=4 * n * (2 * config["dim_in"] + 1))
@@ -121,7 +135,7 @@ def main():
     for config in NETS:
         res = measure(config, n)
         print(json.dumps(res, indent=1))
-        path = os.path.join(out, f"siren_gradient_{config['dim_hidden']}x{config['n_layers']}_n{n}.json")
+        path = os.path.join(out, profile_name(config, n))
         with open(path, "w") as f:
             json.dump(res, f, indent=1)
         print("->", path)
