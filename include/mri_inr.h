@@ -61,7 +61,7 @@ typedef enum mri_deriv_mode {
 typedef struct mri_grid_desc {
   int32_t dim;        /* D, 1..MRI_MAX_DIM                                   */
   int32_t n_levels;   /* L, 1..MRI_MAX_LEVELS                                */
-  int32_t n_features; /* F, 1..8                                             */
+  int32_t n_features; /* F, one of 1, 2, 4, 8 (others are refused)           */
   int32_t reserved;
   float resolution[MRI_MAX_LEVELS][MRI_MAX_DIM + 1]; /* res_l on axis d (float32, as the
                                                         reference multiplies in float32)  */
@@ -148,7 +148,9 @@ int64_t mri_hashgrid_backward_workspace_bytes(const mri_grid_desc* grid, int64_t
 /* Optional split: the first stage of the binned backward (counting the records per table
  * slice) needs only the coordinates, so a trainer can run it on a side stream beside the
  * forward pass and then call mri_hashgrid_backward with `method | MRI_BWD_PREPARED` on the same
- * workspace (same grid, n and method; nothing else may use the workspace in between). */
+ * workspace (same grid, n and method; nothing else may use the workspace in between).  The two calls may be told
+ * different workspace_bytes for that pointer, each at least the reported size: where a region lies depends on the
+ * grid, n, the method and the knobs alone, never on the surplus (tests/test_gpu_workspace.py). */
 #define MRI_BWD_PREPARED 16
 /* `method | MRI_BWD_OVERWRITE`: d_table is OVERWRITTEN with the gradient (every row of every
  * level is written) instead of accumulated into, which saves the caller's memset and the
@@ -294,7 +296,8 @@ int mri_tiny_mlp_train_slice(const float* x, int64_t x_ld, const float* target, 
                              int64_t workspace_bytes, void* stream);
 
 /* mri_tiny_mlp_train[_overwrite] that also reports max |d_x| per PAIR of feature rows: dx_pair_absmax
- * (k_in / 2 non-negative floats) is raised with atomic maxima, so the caller zeroes it before the call.
+ * ((k_in + 1) / 2 non-negative floats: with an odd k_in the last row has an entry of its own) is raised with atomic
+ * maxima, so the caller zeroes it before the call.
  * With a hash-grid encoder of two features per level this is max |dLoss / d features| per level, the scale
  * mri_hashgrid_backward_scaled needs for its gradient records -- taken where d_x is produced instead of by
  * a pass over it.  Served by the bf16-pipe decoder kernel only (mri_tiny_mlp_dx_absmax_supported, else

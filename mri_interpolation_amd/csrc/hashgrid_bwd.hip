@@ -1120,7 +1120,9 @@ int64_t workspace_bytes(const BinPlan& plan, int64_t n, int64_t ws_words, int64_
          2 * chunk_table_words(plan, n) * 4 + ws_words * 8 + records * record_bytes(F) + 80;
 }
 
-// Fixed-position regions first, the record area next, the int64 area at the END of the buffer.
+// Fixed-position regions first, the record area next, the int64 area at the END of the bytes the plan NEEDS
+// (`total_bytes` = workspace_bytes(plan, ...), not what the caller happens to pass: the prepare call clears the
+// int64 area, so the two calls of a prepared pair must find it in one place whatever surplus each was told).
 Workspace carve(void* base, int64_t total_bytes, const BinPlan& plan, int64_t n, int64_t ws_words,
                 int64_t records, int F) {
   Workspace w{};
@@ -1360,7 +1362,7 @@ int backward_impl(const mri_grid_desc* grid, const float* x, const float* d_out,
                 (long long)need, (long long)workspace_bytes_given);
     MRI_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 15) == 0,
                 "workspace must be 16-byte aligned");
-    const Workspace w = carve(workspace, workspace_bytes_given, plan, n, ws_words, records, F);
+    const Workspace w = carve(workspace, need, plan, n, ws_words, records, F);
     const LevelTab tab = make_tab(grid);
     int rc = dispatch<BinnedLaunch>(grid->dim, F, tab, plan, dense, w, grid->n_levels,
                                     level_mask, phase, overwrite, x, d_out, n, sl, sr, sf,

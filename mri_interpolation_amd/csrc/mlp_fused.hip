@@ -1126,8 +1126,11 @@ extern "C" int mri_hash_tiny_mlp_train(const mri_grid_desc* grid, const float* t
               (long long)n);
   const int slab = slab_floats(hidden, k_in);
   const int blocks = x3_blocks(n);
-  MRI_REQUIRE(workspace && workspace_bytes >= (int64_t)blocks * slab * 4,
-              "needs a workspace of %lld bytes (mri_tiny_mlp_workspace_bytes)", (long long)blocks * slab * 4);
+  // (what mri_tiny_mlp_workspace_bytes reports, as for the other training calls: the 64-wide f32-MFMA kernel's
+  // slab count may exceed this kernel's, and one byte less than reported is refused by every call alike)
+  MRI_REQUIRE(workspace && workspace_bytes >= (int64_t)slab_count(hidden, k_in, n) * slab * 4,
+              "needs a workspace of %lld bytes (mri_tiny_mlp_workspace_bytes)",
+              (long long)slab_count(hidden, k_in, n) * slab * 4);
   FusedArgs a{};
   a.target = target;
   a.w1 = w1, a.b1 = b1, a.w2 = w2, a.b2 = b2, a.w3 = w3, a.b3 = b3;

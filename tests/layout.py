@@ -52,6 +52,39 @@ def place(values, offset_floats, ld=None, guard=64):
     return view, check
 
 
+def place_workspace(n_bytes, fill, guard_bytes=None):
+    """A kernel workspace of exactly `n_bytes` (rounded up to the next multiple of 16 for the buffer's own
+    bookkeeping; the call is still told n_bytes) whose start is 16-byte aligned, inside ONE CUDA buffer between two
+    guards of SENTINEL words.  `fill` is the 32-bit pattern the workspace itself holds before the call.  Each guard
+    is at least 1 MiB and at least a quarter of n_bytes (or `guard_bytes`): a slab count that is off by a few
+    workgroups writes into the guard, not outside the allocation.  Returns (workspace, check): `workspace` is the
+    int32 view to take the pointer of (a NULL pointer when n_bytes is 0); check(what) asserts, bit for bit, that
+    both guards are intact and says how many bytes past the end (or before the start) the first stray write lies."""
+    n_bytes = int(n_bytes)
+    assert n_bytes >= 0 and 0 <= fill < 1 << 32
+    body = (n_bytes + 15) // 16 * 16
+    guard = max(1 << 20, (n_bytes + 3) // 4) if guard_bytes is None else int(guard_bytes)
+    guard = (guard + 15) // 16 * 16
+    g, b = guard // 4, body // 4
+    buf = torch.empty(2 * g + b, dtype=torch.int32, device="cuda")
+    assert buf.data_ptr() % 16 == 0
+    buf.fill_(SENTINEL)
+    ws = buf[g:g + b]
+    ws.fill_(fill - (1 << 32) if fill >= 1 << 31 else fill)
+    assert b == 0 or ws.data_ptr() % 16 == 0
+
+    def check(what=""):
+        torch.cuda.synchronize()
+        after = (buf[g + b:] != SENTINEL).nonzero().flatten()
+        assert after.numel() == 0, (f"{what}: {after.numel()} words behind a workspace of {n_bytes} bytes were written, "
+                                    f"the first {body + 4 * int(after[0]) - n_bytes} bytes past its end")
+        before = (buf[:g] != SENTINEL).nonzero().flatten()
+        assert before.numel() == 0, (f"{what}: {before.numel()} words in front of the workspace were written, the "
+                                     f"nearest {4 * (g - int(before[-1]))} bytes before its start")
+
+    return ws, check
+
+
 def variants(widths, lds=True):
     """Layouts of a call's arguments: {name: width of a row, or None for an argument without a leading
     dimension} -> [(tag, {name: (offset, ld)})]: all aligned and packed (the FAST path, under guards too), each

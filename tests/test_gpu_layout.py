@@ -38,6 +38,8 @@ Inventoried by reading only, without a case here: mri_hashgrid_backward_adam, _b
 _prepare (they share mri_hashgrid_backward's kernels and checks; _backward_scaled and _prepare run inside the
 mri_fused_step case), mri_tiny_mlp_train_overlapped (its w2 refusal is mri_tiny_mlp_train_slice's, tested; the call
 itself waits on a producer and stays out of a layout test), mri_sample_indices, mri_tiny_mlp_train_dx_absmax.
+What a workspace may HOLD and how large it must be (exact size between guards, dirty contents, reuse by another shape)
+is tests/test_gpu_workspace.py's subject; here a workspace is only shown to be refused off a 16-byte boundary.
 """
 import ctypes as C
 import functools
