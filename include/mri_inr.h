@@ -547,6 +547,28 @@ int mri_modsiren_backward(const float* x, const float* dy, int64_t n, int32_t di
                           const float* const* sn, float* const* dzs, float* const* dzm,
                           float* const* d_siren_weight, float* const* d_siren_bias, float* const* d_mod_weight,
                           float* const* d_mod_bias, void* workspace, int64_t workspace_bytes, void* stream);
+/* Values AND the gradient with respect to the coordinates of the same network, y (n) and dydx (n, dim_in) row-major,
+ * dydx[i, d] = d y[i] / d x[i, d], in ONE persistent kernel (csrc/modsiren_gradient.hip) instead of autograd through
+ * Modulator.forward (reference models.py:236-260) and the layer loop of ModulatedSirenNet.forward (models.py:311-322).
+ * Forward mode: with Th_l^d = d h_l / d x_d and Ta_l^d = d a_l / d x_d,
+ *   Th_l^d = [pm_l > 0] (.) (Th_{l-1}^d Wm_l[:, :hidden]^T + Wm_l[:, hidden + d])          (ReLU'(0) = 0, as torch)
+ *   Ta_l^d = w_l cos(w_l ps_l) (.) (Ta_{l-1}^d Ws_l^T) (.) h_l + s_l (.) Th_l^d,       dy / dx_d = Ta_{L-1}^d . w_head,
+ * the two products of the value rows on more rows, without bias: a point travels as four consecutive rows (value,
+ * d/dx_0, d/dx_1, d/dx_2) of BOTH LDS images through the tile loop of mri_modsiren_forward's kernel, on the same
+ * bf16x3 form.  Nothing (n, hidden)-sized is written: the call reads n dim_in floats and writes n (1 + dim_in).  No
+ * atomics, a fixed summation order: bitwise reproducible.  At most 256 workgroups walk tiles of 2048 / hidden points.
+ * Supported (mri_modsiren_gradient_supported is the truth): what mri_modsiren_supported accepts with dim_in <= 3;
+ * anything else is refused with MRI_ERR_INVALID_ARGUMENT, the offending argument named in mri_last_error.  n = 0
+ * returns 0 without a launch.  Parameters as mri_modsiren_forward, every weight matrix 16-byte aligned; x, y and dydx
+ * are accessed 4 bytes at a time at any 4-byte aligned address.  workspace: mri_modsiren_gradient_workspace_bytes
+ * device bytes (what mri_modsiren_forward_workspace_bytes reports: the split weights of both stacks; -1 for an
+ * unsupported width or depth), 16-byte aligned; its contents on entry do not matter. */
+int mri_modsiren_gradient_supported(int32_t dim_in, int32_t hidden, int32_t n_layers, int32_t dim_out);
+int64_t mri_modsiren_gradient_workspace_bytes(int32_t hidden, int32_t n_layers);
+int mri_modsiren_gradient(const float* x, int64_t n, int32_t dim_in, int32_t hidden, int32_t n_layers,
+                          const float* const* siren_weight, const float* const* siren_bias,
+                          const float* const* mod_weight, const float* const* mod_bias, float w0_first, float w0,
+                          float* y, float* dydx, void* workspace, int64_t workspace_bytes, void* stream);
 
 /* ---- PsfSirenNet: the acquisition point-spread function -----------------------------------
  * (reference models.py:397-539.)  A target voxel b is the network averaged over S sample points around it:

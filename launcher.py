@@ -55,7 +55,8 @@ def parse_args(argv=None):
                         "path predict does not collect model.latents (as on the other fused paths)")
     p.add_argument("--fused_modulated", action="store_true",
                    help="ModulatedSirenNet: train and predict through the fused modulated SIREN kernel chain "
-                        "(both stacks of a row tile on chip) instead of training_step + autograd")
+                        "(both stacks of a row tile on chip) instead of training_step + autograd; with "
+                        "--save_gradient the gradient volumes come from the fused modulated gradient kernel")
     p.add_argument("--no_batchnorm", action="store_true",
                    help="HashMLP without the BatchNorm1d of its decoder blocks, GELU kept (the notebook's decoder, "
                         "Linear -> GELU twice): trains through the one-kernel shallow decoder step")
@@ -80,7 +81,8 @@ def parse_args(argv=None):
                    help="after pred.nii.gz also write gradient.nii.gz, float32 of shape image_shape + (dim_in,): the "
                         "change of the network's output per voxel step along each axis (models with one output; "
                         "SirenNet / PsfSirenNet through the fused gradient kernel, a 4-D volume's temporal derivative "
-                        "included, the others through autograd), and for every interpolation{shape}.nii.gz a "
+                        "included; ModulatedSirenNet with --fused_modulated through the fused modulated gradient kernel "
+                        "for volumes of up to three axes; the others through autograd), and for every interpolation{shape}.nii.gz a "
                         "gradient_interpolation{shape}.nii.gz of shape + (dim_in,) in voxel steps of THAT grid")
     p.add_argument("--out_dir", type=str, default=None)
     p.add_argument("--max_steps", type=int, default=-1)

@@ -329,9 +329,45 @@ class ModulatedSirenNet(SirenNet):
             x = ops.modulate(layer(x), mod)
         return self.siren.last_layer(x)
 
-    def forward_with_gradient(self, x) -> Tuple[torch.Tensor, torch.Tensor]:
+    def _gradient_plan(self, x):
+        """Arguments of the fused modulated gradient kernel (csrc/modsiren_gradient.hip), or None where the generic
+        body serves: both stacks as the kernel computes them -- sine layers with one w0 behind the first, an identity
+        head, biases everywhere, a shape the kernel takes (dim_in <= 3) -- and a float32 (n, dim_in) tensor on the
+        GPU."""
+        sn = self.siren
+        ls = list(sn.layers) + [sn.last_layer]
+        mods = [seq[0] for seq in self.modulator.layers]
+        if not x.is_cuda or x.dtype != torch.float32 or x.dim() != 2 or any(l.bias is None for l in ls + mods):
+            return None
+        if any(not isinstance(l.activation, Sine) for l in ls[:-1]) or not isinstance(ls[-1].activation, nn.Identity):
+            return None
+        if len({float(l.activation.w0) for l in ls[1:-1]}) > 1:
+            return None
+        hidden, dim_in = ls[0].weight.shape
+        if x.shape[1] != dim_in or len(mods) != len(ls) - 1 or ls[-1].weight.shape != (1, hidden) \
+                or any(l.weight.shape != (hidden, hidden) for l in ls[1:-1]) \
+                or any(m.weight.shape != ((hidden, dim_in) if i == 0 else (hidden, hidden + dim_in))
+                       for i, m in enumerate(mods)):
+            return None
+        if not ops.modsiren_gradient_supported(dim_in, hidden, len(mods), self.dim_out):
+            return None
+        w0_first = float(ls[0].activation.w0)
+        return dict(siren_weights=[l.weight.detach() for l in ls], siren_biases=[l.bias.detach() for l in ls],
+                    mod_weights=[m.weight.detach() for m in mods], mod_biases=[m.bias.detach() for m in mods],
+                    w0_first=w0_first, w0=float(ls[1].activation.w0) if len(ls) > 2 else w0_first)
+
+    def forward_with_gradient(self, x, fused: bool = False) -> Tuple[torch.Tensor, torch.Tensor]:
         """The generic body (autograd through THIS forward): the plain-chain kernel SirenNet dispatches to computes
-        another network."""
+        another network.  `fused` (opt-in, what Trainer(fused_modulated=True) passes): ONE kernel that carries the
+        value and the tangents of a point through both stacks together (ops.modsiren_gradient) where
+        `_gradient_plan` finds it serves; everything else, dim_in >= 4 included, stays the generic body."""
+        if fused:
+            if self.dim_out != 1:
+                raise ValueError(f"forward_with_gradient needs dim_out == 1 (got {self.dim_out})")
+            plan = self._gradient_plan(x)
+            if plan is not None:
+                with torch.no_grad():
+                    return ops.modsiren_gradient(x.detach(), **plan)
         return BaseMLP.forward_with_gradient(self, x)
 
 

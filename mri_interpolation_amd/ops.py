@@ -788,11 +788,12 @@ def modsiren_workspace(n: int, hidden: int, n_layers: int, device) -> torch.Tens
 _modsiren_ws = {}
 
 
-def _modsiren_scratch(device, n, hidden, n_layers, ws):
+def _modsiren_scratch(device, n, hidden, n_layers, ws, need=None):
     if ws is not None:  # the caller's own (FusedStep's, one per batch size): the library checks its size
         _gpu(ws)
         return ws
-    need = _lib.load().mri_modsiren_backward_workspace_bytes(max(int(n), 1), hidden, n_layers)
+    if need is None:  # (the gradient call passes its own: the split weights alone, whatever n)
+        need = _lib.load().mri_modsiren_backward_workspace_bytes(max(int(n), 1), hidden, n_layers)
     if need < 0:  # (the library refuses the shape with its reason)
         return torch.empty(64, dtype=torch.float32, device=device)
     ws = _modsiren_ws.get(device.index)
@@ -840,6 +841,38 @@ def modsiren_forward(x, siren_weights, siren_biases, mod_weights, mod_biases, w0
               _ptr_array(siren_biases), _ptr_array(mod_weights), _ptr_array(mod_biases), float(w0_first), float(w0),
               *arrays, _ptr(y), _ptr(ws), ws.numel() * 4, _stream())
     return y
+
+
+def modsiren_gradient_supported(dim_in: int, hidden: int, n_layers: int, dim_out: int) -> bool:
+    return bool(_lib.load().mri_modsiren_gradient_supported(dim_in, hidden, n_layers, dim_out))
+
+
+def modsiren_gradient(x, siren_weights, siren_biases, mod_weights, mod_biases, w0_first: float, w0: float,
+                      y=None, dydx=None):
+    """(y (n, 1), dydx (n, dim_in)) = ModulatedSirenNet(x) and its gradient with respect to x, dydx[i, d] =
+    dy[i] / dx[i, d], in one persistent kernel (csrc/modsiren_gradient.hip): the value and the dim_in <= 3 tangents
+    of a point travel both stacks together, four rows per point in each of the two LDS images; nothing
+    (n, hidden)-sized is written.  Parameters as modsiren_forward."""
+    _gpu(x, y, dydx, *siren_weights, *siren_biases, *mod_weights, *mod_biases)
+    x = _rowmajor(x).contiguous()
+    n, dim_in = x.shape
+    n_layers, hidden = len(mod_weights), mod_weights[0].shape[0]
+    if len(siren_weights) != n_layers + 1 or len(siren_biases) != n_layers + 1 or len(mod_biases) != n_layers:
+        raise ValueError("modsiren_gradient: n_layers + 1 SIREN weights / biases (the head last), n_layers modulator's")
+    if y is None:
+        y = torch.empty((n, 1), device=x.device, dtype=torch.float32)
+    if dydx is None:
+        dydx = torch.empty((n, dim_in), device=x.device, dtype=torch.float32)
+    if y.numel() != n or dydx.shape != (n, dim_in):
+        raise ValueError("modsiren_gradient: y holds n values, dydx is (n, dim_in)")
+    _modsiren_check("modsiren_gradient", n, hidden, n_layers, {},
+                    list(siren_weights) + list(siren_biases) + list(mod_weights) + list(mod_biases) + [y, dydx])
+    ws = _modsiren_scratch(x.device, n, hidden, n_layers, None,  # holds the split weights
+                           need=_lib.load().mri_modsiren_gradient_workspace_bytes(hidden, n_layers))
+    _lib.call("mri_modsiren_gradient", _ptr(x), n, dim_in, hidden, n_layers, _ptr_array(siren_weights),
+              _ptr_array(siren_biases), _ptr_array(mod_weights), _ptr_array(mod_biases), float(w0_first), float(w0),
+              _ptr(y), _ptr(dydx), _ptr(ws), ws.numel() * 4, _stream())
+    return y, dydx
 
 
 def modsiren_forward_loss(x, target, siren_weights, siren_biases, mod_weights, mod_biases, w0_first: float,

@@ -1341,7 +1341,8 @@ class Trainer:
                  batch_group: int = 1, native_steps: bool = True, fused_batchnorm: bool = False,
                  fused_modulated: bool = False):
         """`fused_modulated`: train (and predict) a ModulatedSirenNet through FusedStep's modulated plan
-        (csrc/modsiren.hip) instead of training_step + autograd (opt-in, like `fused_batchnorm`).
+        (csrc/modsiren.hip) instead of training_step + autograd (opt-in, like `fused_batchnorm`);
+        `predict_with_gradient` then asks the model for its fused coordinate gradient (csrc/modsiren_gradient.hip).
         `fused_batchnorm`: train (and predict) the reference's BatchNorm decoder of HashMLP through
         FusedStep's BatchNorm plan instead of training_step + autograd (opt-in; on this path `predict`
         does not collect `model.latents`, as on the other fused paths).
@@ -1521,13 +1522,15 @@ class Trainer:
     def predict_with_gradient(self, model, dataloaders) -> Tuple[List[torch.Tensor], List[torch.Tensor]]:
         """(per-batch predictions (n, 1), per-batch gradients (n, dim_in) with respect to the coordinates): the
         twin of `predict` through `model.forward_with_gradient` (SirenNet / PsfSirenNet: one fused kernel per
-        batch; every other model: autograd through its forward)."""
+        batch; a ModulatedSirenNet under `fused_modulated=True`: its own fused kernel, csrc/modsiren_gradient.hip,
+        where the shape is covered; every other model: autograd through its forward)."""
         if next(model.parameters()).device.type != "cuda":
             model.cuda()
         model.eval()
+        kwargs = dict(fused=True) if self.fused_modulated and isinstance(model, models.ModulatedSirenNet) else {}
         ys, grads = [], []
         for x, _ in dataloaders:
-            y, g = model.forward_with_gradient(x)
+            y, g = model.forward_with_gradient(x, **kwargs)
             ys.append(y)
             grads.append(g)
         return ys, grads
