@@ -24,6 +24,8 @@
 namespace mri {
 namespace {
 
+constexpr int kAtomicLds = 4096;  // floats: the atomic backward sums levels of up to this many (slots x features) in LDS
+
 struct Sched {  // block -> (level, chunk) map, see decode()
   int affinity;
   int n_levels;
@@ -266,27 +268,53 @@ __global__ __launch_bounds__(256) void hashgrid_bwd_atomic_kernel(
     const LevelTab tab, const Sched sched, const uint32_t level_mask, const float* __restrict__ x,
     const float* __restrict__ d_out, int64_t n, int64_t sl, int64_t sr, int64_t sf,
     float* __restrict__ d_table) {
+  // A level whose whole table fits kAtomicLds floats (the coarse levels: a few hundred slots that every coordinate
+  // of the batch hits) is summed per workgroup in LDS first and leaves as ONE global atomic per touched slot and
+  // workgroup: 256 x 2^D scattered global atomics on the same few lines become at most size x F, and the f32 sum of
+  // a hot slot has sixteen times fewer terms at full magnitude -- the order noise of these sums (two calls on the
+  // same data differ in the last bits) shrinks with it.  (level, chunk) are workgroup-uniform: so are the barriers.
+  __shared__ float lacc[kAtomicLds];
   int level, chunk;
   if (!decode(sched, level, chunk)) return;
   if (!((level_mask >> level) & 1u)) return;
   const int64_t i = (int64_t)chunk * 256 + threadIdx.x;
-  if (i >= n) return;
   const uint32_t size = tab.size[level], magic = tab.magic[level];
   const bool pow2 = tab.pow2[level] != 0;
+  const bool in_lds = (uint64_t)size * F <= (uint64_t)kAtomicLds;
+  const int words = in_lds ? (int)size * F : 0;
   float* __restrict__ rows = d_table + tab.offset[level] * F;
-  const Cell<D> c = locate<D>(x, i, tab.res[level]);
-  float g[F];
-  const float* __restrict__ gp = d_out + (int64_t)level * sl + i * sr;
+  if (in_lds) {
+    for (int e = threadIdx.x; e < words; e += 256) lacc[e] = 0.f;
+    __syncthreads();
+  }
+  if (i < n) {
+    const Cell<D> c = locate<D>(x, i, tab.res[level]);
+    float g[F];
+    const float* __restrict__ gp = d_out + (int64_t)level * sl + i * sr;
 #pragma unroll
-  for (int f = 0; f < F; ++f) g[f] = gp[f * sf];
+    for (int f = 0; f < F; ++f) g[f] = gp[f * sf];
 #pragma unroll kCornerUnroll<D>
-  for (int nb = 0; nb < (1 << D); ++nb) {
-    uint32_t h;
-    float w;
-    corner<D>(c, nb, h, w);
-    float* __restrict__ row = rows + (uint64_t)slot_of(h, size, magic, pow2) * F;
+    for (int nb = 0; nb < (1 << D); ++nb) {
+      uint32_t h;
+      float w;
+      corner<D>(c, nb, h, w);
+      const uint32_t slot = slot_of(h, size, magic, pow2);  // < size
+      if (in_lds) {
 #pragma unroll
-    for (int f = 0; f < F; ++f) atomicAdd(row + f, g[f] * w);
+        for (int f = 0; f < F; ++f) atomicAdd(&lacc[slot * F + f], g[f] * w);
+      } else {
+        float* __restrict__ row = rows + (uint64_t)slot * F;
+#pragma unroll
+        for (int f = 0; f < F; ++f) atomicAdd(row + f, g[f] * w);
+      }
+    }
+  }
+  if (in_lds) {
+    __syncthreads();
+    for (int e = threadIdx.x; e < words; e += 256) {
+      const float v = lacc[e];
+      if (v != 0.f) atomicAdd(rows + e, v);
+    }
   }
 }
 

@@ -551,7 +551,9 @@ __global__ __launch_bounds__(kThreadsR) void siren_forward_rows_kernel(const Cha
             __builtin_amdgcn_sched_barrier(0);
           });
         });
-        if constexpr (i == kTiles) RP_MARK(4)  // the last tile's epilogue, alone
+        // (braces: RP_MARK expands to nothing in the shipped build, and a bare `if constexpr (i == kTiles)` then takes the
+        // range check below as its body -- only the last tile was ever checked)
+        if constexpr (i == kTiles) { RP_MARK(4) }  // the last tile's epilogue, alone
         if constexpr (i > 0) {
           // ---- range check of tile i - 1 (wave-uniform, never taken by a trained network) --------------------------
           constexpr int ti = i - 1;
