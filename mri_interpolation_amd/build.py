@@ -6,6 +6,7 @@ The library is plain HIP behind the C ABI of include/mri_inr.h (no torch types),
 is compiled with hipcc directly -- no torch extension machinery, and the .so travels to
 the GPU box with the source tree.
 """
+import glob
 import os
 import shutil
 import subprocess
@@ -55,8 +56,8 @@ def _stale(target, deps):
 def build(force: bool = False, verbose: bool = False) -> str:
     """Compile every HIP source for gfx950 and link libmri_inr.so; returns its path."""
     os.makedirs(OBJ, exist_ok=True)
-    headers = [os.path.join(CSRC, h) for h in ("common.h", "hashgrid_common.h", "device_math.h", "bf16x3.h",
-                                               "mlp_fused.h", "siren_chain.h")] + [os.path.join(ROOT, "include", "mri_inr.h")]
+    # every header of csrc, by glob: a new one triggers rebuilds without being listed here
+    headers = sorted(glob.glob(os.path.join(CSRC, "*.h"))) + [os.path.join(ROOT, "include", "mri_inr.h")]
     objs, procs = [], []
     for src in SOURCES:
         s = os.path.join(CSRC, src)

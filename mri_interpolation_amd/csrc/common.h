@@ -35,6 +35,9 @@ inline int check_launch(const char* what) {
 
 inline int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
 
+// is p a multiple of `bytes` (a power of two)
+inline bool aligned_to(const void* p, uintptr_t bytes) { return (reinterpret_cast<uintptr_t>(p) & (bytes - 1)) == 0; }
+
 // Tuning knobs (process-wide, speed only -- never change results beyond fp32 summation order), with ONE
 // exception that trades accuracy: bwd_records.
 struct Options {

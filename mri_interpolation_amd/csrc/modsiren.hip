@@ -10,8 +10,8 @@
 //     LDS: a_l (the modulated activation) and h_l (the modulator's hidden state), beside the tile's z = x.  Layer 0
 //     of both stacks (K = dim_in) runs on the VALU.  Every later layer is two H x H products on the bf16 matrix pipe
 //     with three-term operands (bf16x3.h, f32-accurate): a_{l-1} Ws_l^T and h_{l-1} Wm_l[:, :H]^T, both weight
-//     matrices pre-split and streamed from L2 in 16-deep chunks by LDS-DMA (the tile loop of siren_chain.hip, whose
-//     helpers are shared through siren_chain.h).  The dim_in tail columns of Wm_l, the biases, sincos, ReLU and the
+//     matrices pre-split and streamed from L2 in 16-deep chunks by LDS-DMA (the LDS-image tile loop of
+//     chain_tile.h, here with a Ws / Wm pair per chunk).  The dim_in tail columns of Wm_l, the biases, sincos, ReLU and the
 //     product are register work in the epilogue.  Training writes four (n, H) tensors per layer, each once:
 //     a_l, h_l, h_l (.) w_l cos(.) and s_l = sin(.).
 //   modsiren_backward_kernel  the same walk from the head down with the images dzs_l / dzm_l (see there).
@@ -35,16 +35,10 @@ using namespace chain;
 // blocks x CB column blocks.  Half the rows of siren_chain.hip's Shape<H>, so that two images take the ~66 KiB one
 // takes there: 64 rows at H = 128, 128 rows at H = 64.
 template <int HH>
-struct MShape {
-  static constexpr int H = HH;
-  static constexpr int CB = H / 32, RB = 8 / CB;
-  static constexpr int rows = 32 * RB;
-  static constexpr int ld = H + 4;                // image row stride: rows 4 banks apart (mod 64)
-  static constexpr int chunks = H / kKc;          // weight chunks per layer and matrix
-  static constexpr int chunk_bytes = 3 * H * 32;  // three term planes of [H][16] bf16
-  static constexpr int groups = kThreads / H;     // row groups of the (column, row group) phases
-  static constexpr int rpt = rows / groups;       // rows per thread there: 16
-  static_assert(H == 64 || H == 128, "hidden width");
+struct MShape : TileShape<HH, 32> {
+  using T = TileShape<HH, 32>;
+  static constexpr int rpt = T::rows / T::groups;  // rows per thread of the (column, row group) phases: 16
+  static_assert(HH == 64 || HH == 128, "hidden width");
 };
 
 struct ModArgs {
@@ -91,33 +85,30 @@ __global__ __launch_bounds__(kThreads) void modsiren_forward_kernel(const ModArg
   __shared__ MFwdSmem<S> sm;
   constexpr int H = S::H;
   const bool STORE = a.act[0] != nullptr;
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int l31 = lane & 31, lh = lane >> 5;
-  const int rb = wave / S::CB, cb = wave % S::CB;
+  const Lanes<S> ln;
+  const int tid = ln.tid, n0 = ln.n0;  // n0: this lane's output column
   const int L = a.L, n_mm = L - 1;
   const int dim_in = a.dim_in;
 
-  for (int l = 0; l < L; ++l)
-    for (int e = tid; e < H; e += kThreads) sm.bias_s[l][e] = a.bs[l][e], sm.bias_m[l][e] = a.bm[l][e];
-  for (int e = tid; e < H; e += kThreads) sm.w_last[e] = a.ws[L][e];
+  for (int l = 0; l < L; ++l) load_vector<H>(sm.bias_s[l], a.bs[l], tid), load_vector<H>(sm.bias_m[l], a.bm[l], tid);
+  load_vector<H>(sm.w_last, a.ws[L], tid);
   const float b_last = a.bs[L][0];
 
   const int64_t tiles = (a.n + S::rows - 1) / S::rows;
-  const float* a_row = sm.img_a + (rb * 32 + l31) * S::ld + 4 * lh;
-  const float* h_row = sm.img_h + (rb * 32 + l31) * S::ld + 4 * lh;
-  const int n0 = cb * 32 + l31;  // this lane's output column
-  const int boff[1] = {32 * n0 + 16 * (lh ^ ((n0 >> 3) & 1))};
-  const int lane_off = (rb * 32 + 4 * lh) * H + n0;
+  const float* a_row = sm.img_a + ln.fragment_offset();
+  const float* h_row = sm.img_h + ln.fragment_offset();
+  int boff[1];
+  ln.weight_offsets(boff);
+  const int lane_off = ln.global_offset();
   const int64_t smb = split_matrix_bytes(H);
 
+  ChunkStream<S, 1> stream(n_mm, tiles);
   auto issue2 = [&](int layer, int kc, int buf) {  // both matrices of layer `layer` (1 .. L-1), chunk kc
     const char* base = a.wsplit + (int64_t)(2 * (layer - 1)) * smb;
-    issue_chunk<S>(base, kc, sm.wbuf[buf][0], wave, lane);
-    issue_chunk<S>(base + smb, kc, sm.wbuf[buf][1], wave, lane);
+    issue_chunk<S>(base, kc, sm.wbuf[buf][0], ln.wave, ln.lane);
+    issue_chunk<S>(base + smb, kc, sm.wbuf[buf][1], ln.wave, ln.lane);
   };
-  int s = 0;
-  if (n_mm > 0 && (int64_t)blockIdx.x < tiles) issue2(1, 0, 0);
+  stream.prime(issue2);
   float g_loss = 0.f;
 
   for (int64_t tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
@@ -125,10 +116,7 @@ __global__ __launch_bounds__(kThreads) void modsiren_forward_kernel(const ModArg
     const bool full_tile = m0 + S::rows <= a.n;
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();  // previous tile is done with the images / xs / tgt
-    for (int e = tid; e < S::rows * kMaxIn; e += kThreads) {
-      const int row = e / kMaxIn, d = e % kMaxIn;
-      sm.xs[e] = (d < dim_in && m0 + row < a.n) ? a.x[(m0 + row) * dim_in + d] : 0.f;
-    }
+    stage_coords<kMaxIn>(sm.xs, a.x, m0, S::rows, a.n, dim_in, tid);
     if (LOSS && tid < S::rows) sm.tgt[tid] = m0 + tid < a.n ? a.target[m0 + tid] : 0.f;
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();
@@ -180,18 +168,11 @@ __global__ __launch_bounds__(kThreads) void modsiren_forward_kernel(const ModArg
       for (int r = 0; r < 16; ++r) acc_s[0][r] = 0.f, acc_m[0][r] = 0.f;
       x3::Frag fa, fh;
 #pragma unroll
-      for (int kc = 0; kc < S::chunks; ++kc, ++s) {
-        asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-        __builtin_amdgcn_s_barrier();  // chunk s landed for every wave (and the images are complete); the other buffer is free
-        {
-          const bool more_k = kc + 1 < S::chunks;
-          const int nl = more_k ? l : (l < n_mm ? l + 1 : 1);
-          if (more_k || l < n_mm || tile + gridDim.x < tiles) issue2(nl, more_k ? kc + 1 : 0, (s + 1) & 1);
-        }
-        __builtin_amdgcn_sched_barrier(0);
+      for (int kc = 0; kc < S::chunks; ++kc, stream.consumed()) {
+        stream.advance(tile, l, kc, issue2);
         if (kc == 0) fa = first_fragment(a_row), fh = first_fragment(h_row);
-        mma_chunk<1, H>(acc_s, fa, kc + 1 < S::chunks ? a_row + (kc + 1) * kKc : nullptr, sm.wbuf[s & 1][0], boff);
-        mma_chunk<1, H>(acc_m, fh, kc + 1 < S::chunks ? h_row + (kc + 1) * kKc : nullptr, sm.wbuf[s & 1][1], boff);
+        mma_step<S>(acc_s, fa, a_row, kc, sm.wbuf[stream.buffer()][0], boff);
+        mma_step<S>(acc_m, fh, h_row, kc, sm.wbuf[stream.buffer()][1], boff);
       }
       // ---- epilogue: the z tail of the modulator, biases, sincos, ReLU, product ----------------------------------------
       float wt[kMaxIn];
@@ -207,10 +188,10 @@ __global__ __launch_bounds__(kThreads) void modsiren_forward_kernel(const ModArg
       float* __restrict__ gs = STORE ? a.sn[l] + m0 * H : nullptr;
       int off = lane_off;
       asm volatile("" : "+v"(off));
-      const int64_t rows_left = a.n - m0 - rb * 32 - 4 * lh;
+      const int64_t rows_left = ln.rows_left(a.n - m0);
 #pragma unroll
       for (int r = 0; r < 16; r += 2) {
-        const int row = rb * 32 + acc_row(r, lh);
+        const int row = ln.row(r);
         const float4 xa0 = *reinterpret_cast<const float4*>(sm.xs + row * kMaxIn);
         const float4 xb0 = *reinterpret_cast<const float4*>(sm.xs + row * kMaxIn + 4);
         const float4 xa1 = *reinterpret_cast<const float4*>(sm.xs + (row + 1) * kMaxIn);
@@ -230,7 +211,7 @@ __global__ __launch_bounds__(kThreads) void modsiren_forward_kernel(const ModArg
         ph[r] = h0, ph[r + 1] = h1;
         if ((r & 3) == 2) __builtin_amdgcn_sched_barrier(0);  // (else every z read of the epilogue is hoisted to its top: spills)
         if (STORE) {
-          const int dr = (r & 3) + 8 * (r >> 2);
+          const int dr = acc_row(r, 0);
           if (full_tile || dr < rows_left) {
             ga[off + dr * H] = pa[r], gh[off + dr * H] = h0;
             gd[off + dr * H] = h0 * (w0 * c0), gs[off + dr * H] = s0;
@@ -243,29 +224,19 @@ __global__ __launch_bounds__(kThreads) void modsiren_forward_kernel(const ModArg
       }
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
       __builtin_amdgcn_s_barrier();  // every wave has read both images for the last time
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        sm.img_a[(rb * 32 + acc_row(r, lh)) * S::ld + n0] = pa[r];
-        sm.img_h[(rb * 32 + acc_row(r, lh)) * S::ld + n0] = ph[r];
-      }
+      store_acc<S>(sm.img_a, ln, pa);
+      store_acc<S>(sm.img_h, ln, ph);
     }
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();  // image a complete
     // ---- head: y[row] = a_{L-1}[row] . w_head + b_head, one wave per row --------------------------------------------
     {
-      constexpr int kPer = H / 64;
-      float wv[kPer];
-#pragma unroll
-      for (int j = 0; j < kPer; ++j) wv[j] = sm.w_last[lane + 64 * j];
+      const HeadDot<S> head(sm.w_last, ln.lane);
 #pragma unroll 4
       for (int i = 0; i < S::rows / 8; ++i) {
-        const int row = wave * (S::rows / 8) + i;
-        float acc1 = 0.f;
-#pragma unroll
-        for (int j = 0; j < kPer; ++j) acc1 += sm.img_a[row * S::ld + lane + 64 * j] * wv[j];
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) acc1 += __shfl_down(acc1, off, 64);
-        if (lane == 0 && m0 + row < a.n) {
+        const int row = ln.wave * (S::rows / 8) + i;
+        const float acc1 = head(sm.img_a + row * S::ld);
+        if (ln.lane == 0 && m0 + row < a.n) {
           const float yv = acc1 + b_last;
           a.y[m0 + row] = yv;
           if (LOSS) {  // models.py:64 F.mse_loss: mean((y - target)^2); dLoss/dy = 2 (y - t) / N
@@ -280,7 +251,7 @@ __global__ __launch_bounds__(kThreads) void modsiren_forward_kernel(const ModArg
   if (LOSS) {
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     __syncthreads();
-    if (lane == 0) sm.red[wave] = g_loss;
+    if (ln.lane == 0) sm.red[ln.wave] = g_loss;
     __syncthreads();
     if (tid == 0) {
       float sl = 0.f;
@@ -340,18 +311,23 @@ template <class S>
 __global__ __launch_bounds__(kThreads) void modsiren_backward_kernel(const ModBwdArgs a) {
   __shared__ MBwdSmem<S> sm;
   constexpr int H = S::H;
+  // EXCEPTION to the toolkit (chain_tile.h): this kernel keeps its own copies of the lane coordinates, the coordinate
+  // staging, the w_head load, the image write-back and the stream's advance (its order is ChunkStream::advance's, STEP
+  // = -1).  On the helpers it measured 1.60 against 1.44 ms (H = 64) and 2.90 against 2.84 ms (H = 128) per 262144-row
+  // call, six layers; with these copies it runs at the old speed.  A change to the stream order or to acc_row's
+  // callers has to be made here as well.
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int l31 = lane & 31, lh = lane >> 5;
   const int rb = wave / S::CB, cb = wave % S::CB;
+  const int n0 = cb * 32 + l31;
   const int L = a.L, dim_in = a.dim_in;
   for (int e = tid; e < H; e += kThreads) sm.w_last[e] = a.w_head[e];
 
   const int64_t tiles = (a.n + S::rows - 1) / S::rows;
   const float* s_row = sm.img_s + (rb * 32 + l31) * S::ld + 4 * lh;
   const float* m_row = sm.img_m + (rb * 32 + l31) * S::ld + 4 * lh;
-  const int n0 = cb * 32 + l31;
-  const int boff[1] = {32 * n0 + 16 * (lh ^ ((n0 >> 3) & 1))};
+  const int boff[1] = {weight_slot_offset(n0, lh)};
   const int lane_off = (rb * 32 + 4 * lh) * H + n0;
   const int64_t smb = split_matrix_bytes(H);
 
@@ -363,13 +339,13 @@ __global__ __launch_bounds__(kThreads) void modsiren_backward_kernel(const ModBw
   float* const p_wh = p_bs + L * H;
   float* const p_bh = p_wh + H;
 
+  ChunkStream<S, -1> stream(L - 1, tiles);
   auto issue2 = [&](int layer, int kc, int buf) {
     const char* base = a.wtsplit + (int64_t)(2 * (layer - 1)) * smb;
     issue_chunk<S>(base, kc, sm.wbuf[buf][0], wave, lane);
     issue_chunk<S>(base + smb, kc, sm.wbuf[buf][1], wave, lane);
   };
-  int s = 0;
-  if (L > 1 && (int64_t)blockIdx.x < tiles) issue2(L - 1, 0, 0);
+  stream.prime(issue2);
 
   // a saved (n, H) tensor in the accumulator layout (zeros beyond n)
   auto load_acc = [&](const float* __restrict__ src, int64_t m0, bool tile_full, float (&v)[16]) {
@@ -379,7 +355,7 @@ __global__ __launch_bounds__(kThreads) void modsiren_backward_kernel(const ModBw
     const int64_t rows_left = a.n - m0 - rb * 32 - 4 * lh;
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
-      const int dr = (r & 3) + 8 * (r >> 2);
+      const int dr = acc_row(r, 0);
       v[r] = (tile_full || dr < rows_left) ? g[off + dr * H] : 0.f;
     }
   };
@@ -449,7 +425,7 @@ __global__ __launch_bounds__(kThreads) void modsiren_backward_kernel(const ModBw
         const int64_t rows_left = a.n - m0 - rb * 32 - 4 * lh;
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-          const int dr = (r & 3) + 8 * (r >> 2);
+          const int dr = acc_row(r, 0);
           if (full_tile || dr < rows_left) gs[off + dr * H] = zs[r], gz[off + dr * H] = zm[r];
         }
       }
@@ -493,18 +469,18 @@ __global__ __launch_bounds__(kThreads) void modsiren_backward_kernel(const ModBw
       for (int r = 0; r < 16; ++r) acc_s[0][r] = 0.f, acc_m[0][r] = 0.f;
       x3::Frag fs, fm;
 #pragma unroll
-      for (int kc = 0; kc < S::chunks; ++kc, ++s) {
+      for (int kc = 0; kc < S::chunks; ++kc, stream.consumed()) {
         asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
         __builtin_amdgcn_s_barrier();  // chunk s landed for every wave; the other buffer is free
         {
           const bool more_k = kc + 1 < S::chunks;
           const int nl = more_k ? l : (l > 1 ? l - 1 : L - 1);
-          if (more_k || l > 1 || tile + gridDim.x < tiles) issue2(nl, more_k ? kc + 1 : 0, (s + 1) & 1);
+          if (more_k || l > 1 || tile + gridDim.x < tiles) issue2(nl, more_k ? kc + 1 : 0, (stream.s + 1) & 1);
         }
         __builtin_amdgcn_sched_barrier(0);
         if (kc == 0) fs = first_fragment(s_row), fm = first_fragment(m_row);
-        mma_chunk<1, H>(acc_s, fs, kc + 1 < S::chunks ? s_row + (kc + 1) * kKc : nullptr, sm.wbuf[s & 1][0], boff);
-        mma_chunk<1, H>(acc_m, fm, kc + 1 < S::chunks ? m_row + (kc + 1) * kKc : nullptr, sm.wbuf[s & 1][1], boff);
+        mma_chunk<1, H>(acc_s, fs, kc + 1 < S::chunks ? s_row + (kc + 1) * kKc : nullptr, sm.wbuf[stream.s & 1][0], boff);
+        mma_chunk<1, H>(acc_m, fm, kc + 1 < S::chunks ? m_row + (kc + 1) * kKc : nullptr, sm.wbuf[stream.s & 1][1], boff);
       }
 #pragma unroll
       for (int r = 0; r < 16; ++r) da[r] = acc_s[0][r], gm[r] = acc_m[0][r];
@@ -611,19 +587,13 @@ int mod_split(const float* const* ws, const float* const* wm, int dim_in, int hi
 
 int launch_mod_forward(int hidden, const ModArgs& a, int mode, hipStream_t st) {
   const dim3 grid(mod_blocks(hidden, a.n)), block(kThreads);
-  if (hidden == 128) {
-    using S = MShape<128>;
+  return dispatch_hidden_mod(hidden, [&](auto h) {
+    using S = MShape<decltype(h)::value>;
     if (mode == 2) hipLaunchKernelGGL((modsiren_forward_kernel<true, S>), grid, block, 0, st, a);
     else hipLaunchKernelGGL((modsiren_forward_kernel<false, S>), grid, block, 0, st, a);
-  } else {
-    using S = MShape<64>;
-    if (mode == 2) hipLaunchKernelGGL((modsiren_forward_kernel<true, S>), grid, block, 0, st, a);
-    else hipLaunchKernelGGL((modsiren_forward_kernel<false, S>), grid, block, 0, st, a);
-  }
-  return check_launch("modsiren_forward_kernel");
+    return check_launch("modsiren_forward_kernel");
+  });
 }
-
-bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
 // the checks and the argument block the three forward entry points share
 int fill_forward(ModArgs& a, const float* x, int64_t n, int dim_in, int hidden, int L, const float* const* sw,
@@ -644,7 +614,7 @@ int fill_forward(ModArgs& a, const float* x, int64_t n, int dim_in, int hidden, 
     for (int l = 0; l < L; ++l) {
       MRI_REQUIRE(act[l] && hid[l] && dcos[l] && sn[l], "NULL saved-tensor buffer (layer %d)", l);
       // (the backward's weight-gradient kernels stream act / hid in 16-byte pieces: one contract for the four, here too)
-      MRI_REQUIRE(aligned16(act[l]) && aligned16(hid[l]) && aligned16(dcos[l]) && aligned16(sn[l]),
+      MRI_REQUIRE(aligned_to(act[l], 16) && aligned_to(hid[l], 16) && aligned_to(dcos[l], 16) && aligned_to(sn[l], 16),
                   "act / hid / dcos / sn buffers must be 16-byte aligned (layer %d)", l);
       a.act[l] = act[l], a.hid[l] = hid[l], a.dcos[l] = dcos[l], a.sn[l] = sn[l];
     }
@@ -682,7 +652,7 @@ extern "C" int mri_modsiren_forward(const float* x, int64_t n, int32_t dim_in, i
   if (n == 0) return MRI_OK;
   const bool train = act || hid || dcos || sn;
   const int64_t need = mod_split_bytes(hidden, n_layers);
-  MRI_REQUIRE(workspace && workspace_bytes >= need && aligned16(workspace),
+  MRI_REQUIRE(workspace && workspace_bytes >= need && aligned_to(workspace, 16),
               "modulated SIREN forward needs a 16-byte aligned workspace of %lld bytes "
               "(mri_modsiren_forward_workspace_bytes)", (long long)need);
   ModArgs a{};
@@ -708,7 +678,7 @@ extern "C" int mri_modsiren_forward_loss(const float* x, const float* target, in
   if (n == 0) return MRI_OK;
   MRI_REQUIRE(target && dy && loss_out, "NULL pointer");
   const int64_t need = mri_modsiren_backward_workspace_bytes(n, hidden, n_layers);
-  MRI_REQUIRE(workspace && workspace_bytes >= need && aligned16(workspace),
+  MRI_REQUIRE(workspace && workspace_bytes >= need && aligned_to(workspace, 16),
               "modulated SIREN forward with loss needs a 16-byte aligned workspace of %lld bytes "
               "(mri_modsiren_backward_workspace_bytes)", (long long)need);
   ModArgs a{};
@@ -741,7 +711,7 @@ extern "C" int mri_modsiren_backward(const float* x, const float* dy, int64_t n,
                   d_siren_bias && d_mod_weight && d_mod_bias, "NULL pointer");
   const int L = n_layers;
   const int64_t need = mri_modsiren_backward_workspace_bytes(n, hidden, L);
-  MRI_REQUIRE(workspace && workspace_bytes >= need && aligned16(workspace),
+  MRI_REQUIRE(workspace && workspace_bytes >= need && aligned_to(workspace, 16),
               "modulated SIREN backward needs a 16-byte aligned workspace of %lld bytes "
               "(mri_modsiren_backward_workspace_bytes)", (long long)need);
   ModBwdArgs a{};
@@ -757,9 +727,9 @@ extern "C" int mri_modsiren_backward(const float* x, const float* dy, int64_t n,
                 "NULL modulator parameter / gradient pointer (layer %d)", l);
     MRI_REQUIRE(act[l] && hid[l] && dcos[l] && sn[l] && (l == 0 || (dzs[l] && dzm[l])),
                 "NULL saved-tensor buffer (layer %d)", l);
-    MRI_REQUIRE(aligned16(act[l]) && aligned16(hid[l]) && aligned16(dcos[l]) && aligned16(sn[l]),
+    MRI_REQUIRE(aligned_to(act[l], 16) && aligned_to(hid[l], 16) && aligned_to(dcos[l], 16) && aligned_to(sn[l], 16),
                 "act / hid / dcos / sn buffers must be 16-byte aligned (layer %d)", l);
-    MRI_REQUIRE(l == 0 || (aligned16(dzs[l]) && aligned16(dzm[l])), "dzs / dzm buffers must be 16-byte aligned (layer %d)",
+    MRI_REQUIRE(l == 0 || (aligned_to(dzs[l], 16) && aligned_to(dzm[l], 16)), "dzs / dzm buffers must be 16-byte aligned (layer %d)",
                 l);
     r.d_wm[l] = d_mod_weight[l], r.d_bm[l] = d_mod_bias[l];
     a.hid[l] = hid[l], a.dcos[l] = dcos[l], a.sn[l] = sn[l], a.dzs[l] = dzs[l], a.dzm[l] = dzm[l];
@@ -771,11 +741,11 @@ extern "C" int mri_modsiren_backward(const float* x, const float* dy, int64_t n,
   hipStream_t st = (hipStream_t)stream;
   if (int rc = mod_split(siren_weight, mod_weight, dim_in, hidden, L, true, wtsplit, st)) return rc;
   const int blocks = mod_blocks(hidden, n);
-  if (hidden == 128)
-    hipLaunchKernelGGL((modsiren_backward_kernel<MShape<128>>), dim3(blocks), dim3(kThreads), 0, st, a);
-  else
-    hipLaunchKernelGGL((modsiren_backward_kernel<MShape<64>>), dim3(blocks), dim3(kThreads), 0, st, a);
-  if (int rc = check_launch("modsiren_backward_kernel")) return rc;
+  if (int rc = dispatch_hidden_mod(hidden, [&](auto h) {
+        hipLaunchKernelGGL((modsiren_backward_kernel<MShape<decltype(h)::value>>), dim3(blocks), dim3(kThreads), 0, st, a);
+        return check_launch("modsiren_backward_kernel");
+      }))
+    return rc;
   r.partial = a.partial, r.slabs = blocks, r.hidden = hidden, r.L = L, r.dim_in = dim_in;
   hipLaunchKernelGGL(modsiren_bwd_reduce_kernel, dim3((unsigned)ceil_div(mod_slab_floats(hidden, L), 256)), dim3(256),
                      0, st, r);

@@ -13,8 +13,8 @@
 //   dy / dx_d = Ta_{L-1}^d . w_head                                            (ReLU'(0) = 0, as torch)
 //
 // The value row and the tangent rows of both images go through the same two matrix products as more rows, without
-// bias, so the tile loop of modsiren_forward_kernel serves as it is when both images hold, per POINT, four consecutive
-// rows at a 4-aligned position: the value row (a, h) and the tangent rows of x_0, x_1, x_2 (Ta^d, Th^d); rows of absent
+// bias, so the LDS-image tile loop (chain_tile.h), walked as modsiren_forward_kernel walks it with a Ws / Wm pair per
+// layer, serves when both images hold, per POINT, four consecutive rows at a 4-aligned position: the value row (a, h) and the tangent rows of x_0, x_1, x_2 (Ta^d, Th^d); rows of absent
 // axes and of points beyond n are never stored.  The accumulator layout of the 32x32 MFMA (acc_row) puts rows 4 q ..
 // 4 q + 3 of a wave's row block into registers 4 q .. 4 q + 3 of ONE lane: the epilogue, where the tangent rows need
 // the value row's w cos(.), s, h and sign, is lane-local -- no shuffles, no LDS traffic beyond the value row's z --
@@ -38,22 +38,10 @@ constexpr int kSlots = 4;         // image rows of a point: value, d/dx_0, d/dx_
 constexpr int kGradIn = 3;        // axes the slots hold
 constexpr int kMaxBlocks = 256;   // one workgroup per CU
 
-// Geometry of modsiren.hip's MShape (a wave owns a 32 x 32 tile of BOTH layer outputs, the 8 waves are RB row blocks
-// x CB column blocks), the rows counted in points of four image rows.
-template <int HH>
-struct MGShape {
-  static constexpr int H = HH;
-  static constexpr int CB = H / 32, RB = 8 / CB;
-  static constexpr int rows = 32 * RB;              // image rows of a tile: 64 (H = 128), 128 (H = 64)
-  static constexpr int points = rows / kSlots;      // 16, 32
-  static constexpr int ld = H + 4;                  // image row stride: rows 4 banks apart (mod 64)
-  static constexpr int chunks = H / kKc;
-  static constexpr int chunk_bytes = 3 * H * 32;
-  static constexpr int groups = kThreads / H;       // point groups of the first layer's (column, group) mapping
-  static constexpr int ppt = points / groups;       // points per thread there: 4
-  static_assert(H == 64 || H == 128, "hidden width");
-  static_assert(ppt % 2 == 0 && ppt * groups == points, "first-layer mapping");
-};
+// Geometry of modsiren.hip's MShape (a wave owns a 32 x 32 tile of BOTH layer outputs), the rows counted in points of
+// four image rows: 64 rows = 16 points at H = 128, 128 rows = 32 points at H = 64.
+template <int H>
+using MGradShape = TileShape<H, 32, kSlots>;
 
 struct MGradArgs {
   const float* x;  // (n, dim_in)
@@ -84,46 +72,43 @@ template <class S>
 __global__ __launch_bounds__(kThreads) void modsiren_gradient_kernel(const MGradArgs a) {
   __shared__ MGradSmem<S> sm;
   constexpr int H = S::H;
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int l31 = lane & 31, lh = lane >> 5;
-  const int rb = wave / S::CB, cb = wave % S::CB;
+  constexpr int kPpt = S::points / S::groups;  // points per thread of layer 0's (column, group of points) mapping: 4
+  static_assert(H == 64 || H == 128, "hidden width");
+  static_assert(kPpt % 2 == 0 && kPpt * S::groups == S::points, "first-layer mapping");
+  const Lanes<S> ln;
+  const int tid = ln.tid, n0 = ln.n0;  // n0: this lane's output column
   const int L = a.L, n_mm = L - 1;
   const int dim_in = a.dim_in;
 
-  for (int l = 0; l < L; ++l)
-    for (int e = tid; e < H; e += kThreads) sm.bias_s[l][e] = a.bs[l][e], sm.bias_m[l][e] = a.bm[l][e];
-  for (int e = tid; e < H; e += kThreads) sm.w_last[e] = a.ws[L][e];
+  for (int l = 0; l < L; ++l) load_vector<H>(sm.bias_s[l], a.bs[l], tid), load_vector<H>(sm.bias_m[l], a.bm[l], tid);
+  load_vector<H>(sm.w_last, a.ws[L], tid);
   const float b_last = a.bs[L][0];
 
   const int64_t tiles = (a.n + S::points - 1) / S::points;
-  const float* a_row = sm.img_a + (rb * 32 + l31) * S::ld + 4 * lh;
-  const float* h_row = sm.img_h + (rb * 32 + l31) * S::ld + 4 * lh;
-  const int n0 = cb * 32 + l31;  // this lane's output column
-  const int boff[1] = {32 * n0 + 16 * (lh ^ ((n0 >> 3) & 1))};
+  const float* a_row = sm.img_a + ln.fragment_offset();
+  const float* h_row = sm.img_h + ln.fragment_offset();
+  int boff[1];
+  ln.weight_offsets(boff);
   const int64_t smb = split_matrix_bytes(H);
 
+  ChunkStream<S, 1> stream(n_mm, tiles);
   auto issue2 = [&](int layer, int kc, int buf) {  // both matrices of layer `layer` (1 .. L-1), chunk kc
     const char* base = a.wsplit + (int64_t)(2 * (layer - 1)) * smb;
-    issue_chunk<S>(base, kc, sm.wbuf[buf][0], wave, lane);
-    issue_chunk<S>(base + smb, kc, sm.wbuf[buf][1], wave, lane);
+    issue_chunk<S>(base, kc, sm.wbuf[buf][0], ln.wave, ln.lane);
+    issue_chunk<S>(base + smb, kc, sm.wbuf[buf][1], ln.wave, ln.lane);
   };
-  int s = 0;
-  if (n_mm > 0 && (int64_t)blockIdx.x < tiles) issue2(1, 0, 0);
+  stream.prime(issue2);
 
   for (int64_t tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
     const int64_t p0 = tile * S::points;  // first point of the tile
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();  // previous tile is done with the images / xs
-    for (int e = tid; e < S::points * kSlots; e += kThreads) {
-      const int p = e / kSlots, d = e % kSlots;
-      sm.xs[e] = (d < dim_in && p0 + p < a.n) ? a.x[(p0 + p) * dim_in + d] : 0.f;
-    }
+    stage_coords<kSlots>(sm.xs, a.x, p0, S::points, a.n, dim_in, tid);
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();
     // ---- layer 0 of both stacks on the VALU: thread <-> (column, group of points), all four rows of both images ----
     {
-      const int col = tid % H, q0 = (tid / H) * S::ppt;
+      const int col = tid % H, q0 = (tid / H) * kPpt;
       float wsr[kGradIn], wmr[kGradIn];
 #pragma unroll
       for (int d = 0; d < kGradIn; ++d) {  // (0 for an absent axis: its tangent rows come out as zeros)
@@ -133,7 +118,7 @@ __global__ __launch_bounds__(kThreads) void modsiren_gradient_kernel(const MGrad
       const float bsj = sm.bias_s[0][col], bmj = sm.bias_m[0][col];
       const float w0f = a.w0_first;
 #pragma unroll 1
-      for (int i = 0; i < S::ppt; i += 2) {
+      for (int i = 0; i < kPpt; i += 2) {
         float zs0 = 0.f, zs1 = 0.f, zm0 = 0.f, zm1 = 0.f;
 #pragma unroll
         for (int d = 0; d < kGradIn; ++d) {
@@ -164,25 +149,18 @@ __global__ __launch_bounds__(kThreads) void modsiren_gradient_kernel(const MGrad
         }
       }
     }
-    // ---- H x H layers: the forward kernel's loop, two products per layer ----------------------------------------------
+    // ---- H x H layers: two products per layer ------------------------------------------------------------------------
     for (int l = 1; l <= n_mm; ++l) {
       f32x16 acc_s[1], acc_m[1];
 #pragma unroll
       for (int r = 0; r < 16; ++r) acc_s[0][r] = 0.f, acc_m[0][r] = 0.f;
       x3::Frag fa, fh;
 #pragma unroll
-      for (int kc = 0; kc < S::chunks; ++kc, ++s) {
-        asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-        __builtin_amdgcn_s_barrier();  // chunk s landed for every wave (and the images are complete); the other buffer is free
-        {
-          const bool more_k = kc + 1 < S::chunks;
-          const int nl = more_k ? l : (l < n_mm ? l + 1 : 1);
-          if (more_k || l < n_mm || tile + gridDim.x < tiles) issue2(nl, more_k ? kc + 1 : 0, (s + 1) & 1);
-        }
-        __builtin_amdgcn_sched_barrier(0);
+      for (int kc = 0; kc < S::chunks; ++kc, stream.consumed()) {
+        stream.advance(tile, l, kc, issue2);
         if (kc == 0) fa = first_fragment(a_row), fh = first_fragment(h_row);
-        mma_chunk<1, H>(acc_s, fa, kc + 1 < S::chunks ? a_row + (kc + 1) * kKc : nullptr, sm.wbuf[s & 1][0], boff);
-        mma_chunk<1, H>(acc_m, fh, kc + 1 < S::chunks ? h_row + (kc + 1) * kKc : nullptr, sm.wbuf[s & 1][1], boff);
+        mma_step<S>(acc_s, fa, a_row, kc, sm.wbuf[stream.buffer()][0], boff);
+        mma_step<S>(acc_m, fh, h_row, kc, sm.wbuf[stream.buffer()][1], boff);
       }
       // ---- epilogue: registers 4 q .. 4 q + 3 are one point's value and tangent rows of both products ----------------
       float wt[kGradIn];
@@ -194,7 +172,7 @@ __global__ __launch_bounds__(kThreads) void modsiren_gradient_kernel(const MGrad
 #pragma unroll
       for (int q = 0; q < 4; q += 2) {
         // the points of registers 4 q and 4 q + 4: image rows rb 32 + 8 q + 4 lh and + 8
-        const int pt = rb * (32 / kSlots) + 2 * q + lh;
+        const int pt = ln.rb * (32 / kSlots) + 2 * q + ln.lh;
         const float4 x0 = *reinterpret_cast<const float4*>(sm.xs + pt * kSlots);
         const float4 x1 = *reinterpret_cast<const float4*>(sm.xs + (pt + 2) * kSlots);
         float t0 = x0.x * wt[0], t1 = x1.x * wt[0];
@@ -219,32 +197,22 @@ __global__ __launch_bounds__(kThreads) void modsiren_gradient_kernel(const MGrad
       }
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
       __builtin_amdgcn_s_barrier();  // every wave has read both images for the last time
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        sm.img_a[(rb * 32 + acc_row(r, lh)) * S::ld + n0] = pa[r];
-        sm.img_h[(rb * 32 + acc_row(r, lh)) * S::ld + n0] = ph[r];
-      }
+      store_acc<S>(sm.img_a, ln, pa);
+      store_acc<S>(sm.img_h, ln, ph);
     }
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();  // image a complete
     // ---- head: image row of a . w_head, one wave per row; slot 0 -> y (+ bias), slot 1 + d -> dydx[:, d] -----------
     {
-      constexpr int kPer = H / 64;
-      float wv[kPer];
-#pragma unroll
-      for (int j = 0; j < kPer; ++j) wv[j] = sm.w_last[lane + 64 * j];
+      const HeadDot<S> head(sm.w_last, ln.lane);
 #pragma unroll 4
       for (int i = 0; i < S::rows / 8; ++i) {
-        const int row = wave * (S::rows / 8) + i;  // wave-uniform
+        const int row = ln.wave * (S::rows / 8) + i;  // wave-uniform
         const int slot = row % kSlots;
         const int64_t p = p0 + row / kSlots;
         if (slot - 1 >= dim_in || p >= a.n) continue;
-        float acc1 = 0.f;
-#pragma unroll
-        for (int j = 0; j < kPer; ++j) acc1 += sm.img_a[row * S::ld + lane + 64 * j] * wv[j];
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) acc1 += __shfl_down(acc1, off, 64);
-        if (lane == 0) {
+        const float acc1 = head(sm.img_a + row * S::ld);
+        if (ln.lane == 0) {
           if (slot == 0)
             a.y[p] = acc1 + b_last;
           else
@@ -261,11 +229,9 @@ bool mgrad_supported(int dim_in, int hidden, int n_layers, int dim_out) {
 
 int64_t mgrad_split_bytes(int hidden, int L) { return 2 * (int64_t)(L - 1) * split_matrix_bytes(hidden); }
 
-bool aligned_to(const void* p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
-
 template <int H>
 int launch_mgrad(const MGradArgs& a, hipStream_t st) {
-  using S = MGShape<H>;
+  using S = MGradShape<H>;
   const int blocks = (int)std::min<int64_t>(ceil_div(a.n, S::points), kMaxBlocks);
   hipLaunchKernelGGL((modsiren_gradient_kernel<S>), dim3(blocks), dim3(kThreads), 0, st, a);
   return check_launch("modsiren_gradient_kernel");
@@ -298,16 +264,10 @@ extern "C" int mri_modsiren_gradient(const float* x, int64_t n, int32_t dim_in, 
               n_layers, kMaxSine);
   MRI_REQUIRE(mgrad_supported(dim_in, hidden, n_layers, 1), "modulated SIREN gradient: %d -> %d x %d -> 1 is not supported",
               dim_in, hidden, n_layers);
-  MRI_REQUIRE(n >= 0 && n < (1ll << 31), "n = %lld out of range", (long long)n);
+  if (int rc = check_gradient_io(x, n, y, dydx)) return rc;
   if (n == 0) return MRI_OK;
-  MRI_REQUIRE(x, "x is NULL");
   MRI_REQUIRE(siren_weight && siren_bias, "siren_weight / siren_bias is NULL");
   MRI_REQUIRE(mod_weight && mod_bias, "mod_weight / mod_bias is NULL");
-  MRI_REQUIRE(y, "y is NULL");
-  MRI_REQUIRE(dydx, "dydx is NULL");
-  MRI_REQUIRE(aligned_to(x, 4), "x must be 4-byte aligned");
-  MRI_REQUIRE(aligned_to(y, 4), "y must be 4-byte aligned");
-  MRI_REQUIRE(aligned_to(dydx, 4), "dydx must be 4-byte aligned");
   const int64_t need = mgrad_split_bytes(hidden, n_layers);
   MRI_REQUIRE(workspace && workspace_bytes >= need && aligned_to(workspace, 16),
               "workspace: the modulated SIREN gradient needs %lld bytes, 16-byte aligned "
@@ -331,5 +291,5 @@ extern "C" int mri_modsiren_gradient(const float* x, int64_t n, int32_t dim_in, 
   if (int rc = split_weights_ld(siren_weight + 1, n_layers - 1, hidden, hidden, false, out, 2 * smb, st)) return rc;
   if (int rc = split_weights_ld(mod_weight + 1, n_layers - 1, hidden, hidden + dim_in, false, out + smb, 2 * smb, st))
     return rc;
-  return hidden == 128 ? launch_mgrad<128>(a, st) : launch_mgrad<64>(a, st);
+  return dispatch_hidden_mod(hidden, [&](auto h) { return launch_mgrad<decltype(h)::value>(a, st); });
 }

@@ -46,27 +46,18 @@
 namespace mri {
 namespace {
 
-using namespace chain;  // tile-loop helpers shared with modsiren.hip (siren_chain.h)
+using namespace chain;  // the LDS-image tile loop (chain_tile.h)
 
 constexpr int kWr = 32;        // batch rows per chunk of the weight-gradient kernel
 
-// Geometry for hidden width H: a wave owns a 32 x CT tile of the (rows x H) layer output, the 8
-// waves are RB row blocks x CB column blocks, so narrower networks take taller tiles and every
-// shape keeps ~64 KiB of activation image and 32 MFMAs per wave and chunk (16 for H = 32).
+// Geometry for hidden width H (TileShape): a wave owns a 32 x 64 tile (32 x 32 at H = 32), so the tiles have 64, 128,
+// 256, 256 rows for H = 256 .. 32 and every shape keeps ~64 KiB of activation image and 32 MFMAs per wave and chunk
+// (16 for H = 32).
 template <int HH>
-struct Shape {
-  static constexpr int H = HH;
-  static constexpr int CT = H < 64 ? H : 64;        // columns of a wave's tile
-  static constexpr int NT = CT / 32;                // 32 x 32 MFMA tiles per wave
-  static constexpr int CB = H / CT, RB = 8 / CB;    // column / row blocks of the 8 waves
-  static constexpr int rows = 32 * RB;              // rows of a tile: 64, 128, 256, 256
-  static constexpr int ld = H + 4;                  // image row stride: rows 4 banks apart (mod 64)
-  static constexpr int chunks = H / kKc;            // weight chunks per layer
-  static constexpr int chunk_bytes = 3 * H * 32;    // a weight chunk: three term planes of [H][16] bf16
-  static constexpr int groups = kThreads / H;       // row groups of the (column, row group) phases
-  static constexpr int rpt = rows / groups;         // rows per thread there: 32 (16 for H = 32)
-  static constexpr int drip = 16 / chunks;          // accumulator registers dripped per chunk
-  static_assert(H == 32 || H == 64 || H == 128 || H == 256, "hidden width");
+struct Shape : TileShape<HH, 64> {
+  using T = TileShape<HH, 64>;
+  static constexpr int rpt = T::rows / T::groups;   // rows per thread of the (column, row group) phases: 32 (16 for H = 32)
+  static constexpr int drip = 16 / T::chunks;       // accumulator registers dripped per chunk
 };
 
 template <class S>
@@ -107,29 +98,26 @@ __global__ __launch_bounds__(kThreads) void siren_forward_kernel(const ChainArgs
   __shared__ FwdSmem<S> sm;
   constexpr int H = S::H, NT = S::NT;
   constexpr bool STORE = MODE >= 1, LOSS = MODE == 2;
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int l31 = lane & 31, lh = lane >> 5;
-  const int rb = wave / S::CB, cb = wave % S::CB;
+  const Lanes<S> ln;
+  const int tid = ln.tid, n0 = ln.n0;  // n0: the lane's column of MFMA tile 0; tile t: + 32 t
   const int n_mm = a.n_sine - 1;  // H x H layers
 
   // ---- small resident parameters ------------------------------------------------------------
-  for (int l = 0; l < a.n_sine; ++l)
-    for (int e = tid; e < H; e += kThreads) sm.bias[l][e] = a.b[l][e];
-  for (int e = tid; e < H; e += kThreads) sm.w_last[e] = a.w[a.n_sine][e];
+  for (int l = 0; l < a.n_sine; ++l) load_vector<H>(sm.bias[l], a.b[l], tid);
+  load_vector<H>(sm.w_last, a.w[a.n_sine], tid);
   const float b_last = a.b[a.n_sine][0];
 
   const int64_t tiles = (a.n + S::rows - 1) / S::rows;
   // this lane's fragment addresses
-  const float* a_row = sm.img + (rb * 32 + l31) * S::ld + 4 * lh;
-  const int n0 = cb * S::CT + l31;  // column of tile 0; tile t: + 32 t
+  const float* a_row = sm.img + ln.fragment_offset();
   int boff[NT];
-#pragma unroll
-  for (int t = 0; t < NT; ++t) boff[t] = 32 * (n0 + 32 * t) + 16 * (lh ^ (((n0 + 32 * t) >> 3) & 1));
+  ln.weight_offsets(boff);
 
-  // chunk stream: chunk s (layer 1 + (s / chunks) % n_mm, columns 32 (s % chunks)) lives in wbuf[s & 1]
-  int s = 0;
-  if (n_mm > 0 && (int64_t)blockIdx.x < tiles) issue_chunk<S>(a.wsplit, 0, sm.wbuf[0], wave, lane);
+  ChunkStream<S, 1> stream(n_mm, tiles);
+  auto issue = [&](int layer, int kc, int buf) {  // the matrix of layer `layer` (1 .. n_mm), chunk kc
+    issue_chunk<S>(a.wsplit + (layer - 1) * split_matrix_bytes(H), kc, sm.wbuf[buf], ln.wave, ln.lane);
+  };
+  stream.prime(issue);
 
   // activations waiting to leave for HBM (STORE): the outputs of MFMA layer `pend_l` of the tile
   // at `pend_m0`, dripped out a few registers per chunk beside the next layer's MFMAs
@@ -140,7 +128,7 @@ __global__ __launch_bounds__(kThreads) void siren_forward_kernel(const ChainArgs
 #pragma unroll
   for (int t = 0; t < NT; ++t) g_wh[t] = g_bl[t] = 0.f;
   // lane's element offset inside a tile's (rows, H) block for accumulator register 0 of tile 0
-  const int lane_off = (rb * 32 + 4 * lh) * H + n0;
+  const int lane_off = ln.global_offset();
   auto drip = [&](int r_lo, int r_hi, bool tile_full) {
     if (!STORE || pend_l < 0) return;
     // uniform bases + a 32-bit lane offset; the offset is re-derived from an opaque copy per call,
@@ -149,13 +137,13 @@ __global__ __launch_bounds__(kThreads) void siren_forward_kernel(const ChainArgs
     float* __restrict__ gd = a.deriv[pend_l] + pend_m0 * H;
     int off = lane_off;
     asm volatile("" : "+v"(off));
-    const int64_t rows_left = a.n - pend_m0 - rb * 32 - 4 * lh;  // rows below this one are live
+    const int64_t rows_left = ln.rows_left(a.n - pend_m0);  // rows below this one are live
 #pragma unroll
     for (int t = 0; t < NT; ++t)
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
         if (r < r_lo || r >= r_hi) continue;
-        const int dr = (r & 3) + 8 * (r >> 2);
+        const int dr = acc_row(r, 0);
         if (tile_full || dr < rows_left) {  // tile_full is wave-uniform: no per-store branches
           ga[off + dr * H + t * 32] = pa[t][r];
           gd[off + dr * H + t * 32] = pd[t][r];
@@ -170,10 +158,7 @@ __global__ __launch_bounds__(kThreads) void siren_forward_kernel(const ChainArgs
     // ---- x tile -> LDS -------------------------------------------------------------------------
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();  // previous tile is done with img / xs
-    for (int e = tid; e < S::rows * kMaxIn; e += kThreads) {
-      const int row = e / kMaxIn, d = e % kMaxIn;
-      sm.xs[e] = (d < a.dim_in && m0 + row < a.n) ? a.x[(m0 + row) * a.dim_in + d] : 0.f;
-    }
+    stage_coords<kMaxIn>(sm.xs, a.x, m0, S::rows, a.n, a.dim_in, tid);
     if (LOSS && tid < S::rows) sm.tgt[tid] = m0 + tid < a.n ? a.target[m0 + tid] : 0.f;
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();
@@ -218,29 +203,12 @@ __global__ __launch_bounds__(kThreads) void siren_forward_kernel(const ChainArgs
         for (int r = 0; r < 16; ++r) acc[t][r] = 0.f;
       x3::Frag fa;
 #pragma unroll
-      for (int kc = 0; kc < S::chunks; ++kc, ++s) {
-        // Chunk s has landed (this wave's own pieces; vmcnt counts loads, stores and LDS-DMA
-        // together).  The stores dripped at the start of the previous chunk have had a whole
-        // chunk to retire, so waiting for everything costs nothing: counted waits that left them
-        // in flight measured 6.27 against 6.29 ms per 2^20-row pass.
-#ifndef SIREN_EXPERIMENT_NO_DMA_WAIT  // timing experiment only (results are then wrong)
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#endif
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        __builtin_amdgcn_s_barrier();  // ... for every wave, and wbuf[(s + 1) & 1] is free
-        SP_MARK(2)  // chunk wait + barrier
-        {
-          const bool more_k = kc + 1 < S::chunks;
-          const int nl = more_k ? l : (l < n_mm ? l + 1 : 1);
-          if (more_k || l < n_mm || tile + gridDim.x < tiles)
-            issue_chunk<S>(a.wsplit + (nl - 1) * split_matrix_bytes(H), more_k ? kc + 1 : 0,
-                           sm.wbuf[(s + 1) & 1], wave, lane);
-        }
-        __builtin_amdgcn_sched_barrier(0);
+      for (int kc = 0; kc < S::chunks; ++kc, stream.consumed()) {
+        stream.advance(tile, l, kc, issue, [&] { SP_MARK(2) });  // mark: chunk wait + barrier
         drip(kc * S::drip, (kc + 1) * S::drip, full_tile);
         SP_MARK(3)  // DMA issue + dripped stores
-        if (kc == 0) fa = first_fragment(a_row);  // (the barrier above completed the image)
-        mma_chunk<NT, H>(acc, fa, kc + 1 < S::chunks ? a_row + (kc + 1) * kKc : nullptr, sm.wbuf[s & 1], boff);
+        if (kc == 0) fa = first_fragment(a_row);  // (the stream's barrier completed the image)
+        mma_step<S>(acc, fa, a_row, kc, sm.wbuf[stream.buffer()], boff);
         SP_MARK(4)  // fragment reads + MFMAs
       }
       pend_l = -1;  // fully dripped
@@ -261,10 +229,7 @@ __global__ __launch_bounds__(kThreads) void siren_forward_kernel(const ChainArgs
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
       __builtin_amdgcn_s_barrier();  // every wave has read the image for the last time
 #pragma unroll
-      for (int t = 0; t < NT; ++t)
-#pragma unroll
-        for (int r = 0; r < 16; ++r)
-          sm.img[(rb * 32 + acc_row(r, lh)) * S::ld + n0 + t * 32] = pa[t][r];
+      for (int t = 0; t < NT; ++t) store_acc<S>(sm.img, ln, pa[t], t);
       if (STORE) {
         pend_l = l, pend_m0 = m0;
         if (l == n_mm) {  // no next MFMA layer in this tile: leave now (loss mode: stay on chip)
@@ -278,20 +243,12 @@ __global__ __launch_bounds__(kThreads) void siren_forward_kernel(const ChainArgs
     __builtin_amdgcn_s_barrier();  // image complete
     // ---- head: y[row] = img[row] . w_last + b_last, one wave per row ---------------------------
     {
-      constexpr int kPer = H >= 64 ? H / 64 : 1;  // elements per lane (H = 32: half the lanes)
-      float wv[kPer];
-#pragma unroll
-      for (int j = 0; j < kPer; ++j) wv[j] = lane + 64 * j < H ? sm.w_last[lane + 64 * j] : 0.f;
+      const HeadDot<S> head(sm.w_last, ln.lane);
 #pragma unroll 4
       for (int i = 0; i < S::rows / 8; ++i) {
-        const int row = wave * (S::rows / 8) + i;
-        float acc1 = 0.f;
-#pragma unroll
-        for (int j = 0; j < kPer; ++j)
-          if (lane + 64 * j < H) acc1 += sm.img[row * S::ld + lane + 64 * j] * wv[j];
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) acc1 += __shfl_down(acc1, off, 64);
-        if (lane == 0 && m0 + row < a.n) {
+        const int row = ln.wave * (S::rows / 8) + i;
+        const float acc1 = head(sm.img + row * S::ld);
+        if (ln.lane == 0 && m0 + row < a.n) {
           const float yv = acc1 + b_last;
           a.y[m0 + row] = yv;
           if (LOSS) {  // models.py:64 F.mse_loss: mean((y - target)^2); dLoss/dy = 2 (y - t) / N
@@ -301,7 +258,7 @@ __global__ __launch_bounds__(kThreads) void siren_forward_kernel(const ChainArgs
             g_bhead += dyv;
             sm.tgt[row] = dyv;
           }
-        } else if (LOSS && lane == 0) {
+        } else if (LOSS && ln.lane == 0) {
           sm.tgt[row] = 0.f;
         }
       }
@@ -313,14 +270,14 @@ __global__ __launch_bounds__(kThreads) void siren_forward_kernel(const ChainArgs
       float* __restrict__ gz = a.dz_last + m0 * H;
       int off = lane_off;
       asm volatile("" : "+v"(off));
-      const int64_t rows_left = a.n - m0 - rb * 32 - 4 * lh;
+      const int64_t rows_left = ln.rows_left(a.n - m0);
 #pragma unroll
       for (int t = 0; t < NT; ++t) {
         const float wl = sm.w_last[n0 + 32 * t];
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-          const int dr = (r & 3) + 8 * (r >> 2);
-          const float dyv = sm.tgt[rb * 32 + 4 * lh + dr];
+          const int dr = acc_row(r, 0);
+          const float dyv = sm.tgt[ln.row(r)];
           g_wh[t] += dyv * pa[t][r];
           const float dz = (dyv * wl) * pd[t][r];
           g_bl[t] += dz;
@@ -341,9 +298,9 @@ __global__ __launch_bounds__(kThreads) void siren_forward_kernel(const ChainArgs
     for (int t = 0; t < NT; ++t) {
       const float wh = g_wh[t] + __shfl_xor(g_wh[t], 32, 64);  // the lane halves hold different rows
       const float bl = g_bl[t] + __shfl_xor(g_bl[t], 32, 64);
-      if (lh == 0) {
-        red[rb * H + n0 + 32 * t] = wh;
-        red[(S::RB + rb) * H + n0 + 32 * t] = bl;
+      if (ln.lh == 0) {
+        red[ln.rb * H + n0 + 32 * t] = wh;
+        red[(S::RB + ln.rb) * H + n0 + 32 * t] = bl;
       }
     }
     __syncthreads();
@@ -355,8 +312,8 @@ __global__ __launch_bounds__(kThreads) void siren_forward_kernel(const ChainArgs
       slab[H + tid] = bl;
     }
     __syncthreads();
-    red[tid] = lane == 0 ? g_bhead : 0.f;  // lane 0 of each wave holds its rows' sums
-    red[kThreads + tid] = lane == 0 ? g_loss : 0.f;
+    red[tid] = ln.lane == 0 ? g_bhead : 0.f;  // lane 0 of each wave holds its rows' sums
+    red[kThreads + tid] = ln.lane == 0 ? g_loss : 0.f;
     __syncthreads();
     if (tid == 0) {
       float sb = 0.f, sl = 0.f;
@@ -393,20 +350,16 @@ template <class S>
 __global__ __launch_bounds__(kThreads) void siren_backward_kernel(const BwdArgs a) {
   __shared__ BwdSmem<S> sm;
   constexpr int H = S::H, NT = S::NT;
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int l31 = lane & 31, lh = lane >> 5;
-  const int rb = wave / S::CB, cb = wave % S::CB;
+  const Lanes<S> ln;
+  const int tid = ln.tid, n0 = ln.n0;
   const int L = a.n_sine;  // sine layers 0 .. L-1, head = layer L
-  for (int e = tid; e < H; e += kThreads) sm.w_last[e] = a.w[L][e];
+  load_vector<H>(sm.w_last, a.w[L], tid);
 
   const int64_t tiles = (a.n + S::rows - 1) / S::rows;
-  const float* a_row = sm.img + (rb * 32 + l31) * S::ld + 4 * lh;
-  const int n0 = cb * S::CT + l31;
-  const int lane_off = (rb * 32 + 4 * lh) * H + n0;  // element (row of register 0, column n0)
+  const float* a_row = sm.img + ln.fragment_offset();
+  const int lane_off = ln.global_offset();  // element (row of register 0, column n0)
   int boff[NT];
-#pragma unroll
-  for (int t = 0; t < NT; ++t) boff[t] = 32 * (n0 + 32 * t) + 16 * (lh ^ (((n0 + 32 * t) >> 3) & 1));
+  ln.weight_offsets(boff);
   const int col = tid % H, r0 = (tid / H) * S::rpt;  // VALU phases: (column, group of rows)
 
   // running sums of this workgroup
@@ -416,9 +369,11 @@ __global__ __launch_bounds__(kThreads) void siren_backward_kernel(const BwdArgs 
 #pragma unroll
   for (int d = 0; d < kMaxIn; ++d) g_wfirst[d] = 0.f;
 
-  int s = 0;
-  if (L > 1 && (int64_t)blockIdx.x < tiles)
-    issue_chunk<S>(a.wtsplit + (L - 2) * split_matrix_bytes(H), 0, sm.wbuf[0], wave, lane);
+  ChunkStream<S, -1> stream(L - 1, tiles);
+  auto issue = [&](int layer, int kc, int buf) {  // the matrix of layer `layer` (1 .. L-1), chunk kc
+    issue_chunk<S>(a.wtsplit + (layer - 1) * split_matrix_bytes(H), kc, sm.wbuf[buf], ln.wave, ln.lane);
+  };
+  stream.prime(issue);
 
   float pz[NT][16];  // dz waiting to leave for HBM, dripped beside the next layer's MFMAs
   int pend_l = -1;
@@ -428,13 +383,13 @@ __global__ __launch_bounds__(kThreads) void siren_backward_kernel(const BwdArgs 
     float* __restrict__ gz = a.dz[pend_l] + pend_m0 * H;
     int off = lane_off;
     asm volatile("" : "+v"(off));
-    const int64_t rows_left = a.n - pend_m0 - rb * 32 - 4 * lh;
+    const int64_t rows_left = ln.rows_left(a.n - pend_m0);
 #pragma unroll
     for (int t = 0; t < NT; ++t)
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
         if (r < r_lo || r >= r_hi) continue;
-        const int dr = (r & 3) + 8 * (r >> 2);
+        const int dr = acc_row(r, 0);
         if (tile_full || dr < rows_left) gz[off + dr * H + t * 32] = pz[t][r];
       }
   };
@@ -443,12 +398,12 @@ __global__ __launch_bounds__(kThreads) void siren_backward_kernel(const BwdArgs 
     const float* __restrict__ g = d + m0 * H;
     int off = lane_off;
     asm volatile("" : "+v"(off));
-    const int64_t rows_left = a.n - m0 - rb * 32 - 4 * lh;
+    const int64_t rows_left = ln.rows_left(a.n - m0);
 #pragma unroll
     for (int t = 0; t < NT; ++t)
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
-        const int dr = (r & 3) + 8 * (r >> 2);
+        const int dr = acc_row(r, 0);
         dv[t][r] = (tile_full || dr < rows_left) ? g[off + dr * H + t * 32] : 0.f;
       }
   };
@@ -458,10 +413,7 @@ __global__ __launch_bounds__(kThreads) void siren_backward_kernel(const BwdArgs 
     const bool full_tile = m0 + S::rows <= a.n;
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();  // previous tile is done with img / xs / dy
-    for (int e = tid; e < S::rows * kMaxIn; e += kThreads) {
-      const int row = e / kMaxIn, d = e % kMaxIn;
-      sm.xs[e] = (d < a.dim_in && m0 + row < a.n) ? a.x[(m0 + row) * a.dim_in + d] : 0.f;
-    }
+    stage_coords<kMaxIn>(sm.xs, a.x, m0, S::rows, a.n, a.dim_in, tid);
     if (!a.head_done && tid < S::rows) {
       const float v = m0 + tid < a.n ? a.dy[m0 + tid] : 0.f;
       sm.dy[tid] = v;
@@ -517,21 +469,12 @@ __global__ __launch_bounds__(kThreads) void siren_backward_kernel(const BwdArgs 
       float dv[NT][16];
       x3::Frag fa;
 #pragma unroll
-      for (int kc = 0; kc < S::chunks; ++kc, ++s) {
-        asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-        __builtin_amdgcn_s_barrier();  // chunk s landed for every wave; the other buffer is free
-        {
-          const bool more_k = kc + 1 < S::chunks;
-          const int nl = more_k ? l : (l > 1 ? l - 1 : L - 1);
-          if (more_k || l > 1 || tile + gridDim.x < tiles)
-            issue_chunk<S>(a.wtsplit + (nl - 1) * split_matrix_bytes(H), more_k ? kc + 1 : 0,
-                           sm.wbuf[(s + 1) & 1], wave, lane);
-        }
-        __builtin_amdgcn_sched_barrier(0);
+      for (int kc = 0; kc < S::chunks; ++kc, stream.consumed()) {
+        stream.advance(tile, l, kc, issue);
         drip(kc * S::drip, (kc + 1) * S::drip, full_tile);
         if (kc == 0) load_deriv(a.deriv[l - 1], m0, full_tile, dv);  // lands beside the MFMAs
-        if (kc == 0) fa = first_fragment(a_row);  // (the barrier above completed the image)
-        mma_chunk<NT, H>(acc, fa, kc + 1 < S::chunks ? a_row + (kc + 1) * kKc : nullptr, sm.wbuf[s & 1], boff);
+        if (kc == 0) fa = first_fragment(a_row);  // (the stream's barrier completed the image)
+        mma_step<S>(acc, fa, a_row, kc, sm.wbuf[stream.buffer()], boff);
       }
       pend_l = -1;
 #pragma unroll
@@ -544,15 +487,12 @@ __global__ __launch_bounds__(kThreads) void siren_backward_kernel(const BwdArgs 
         }
         sum += __shfl_xor(sum, 32, 64);  // the two lane halves hold different rows of one column
         // (layer, row block, column) has exactly one owner lane: plain read-add-write
-        if (lh == 0) sm.gb[l - 1][rb][n0 + 32 * t] += sum;
+        if (ln.lh == 0) sm.gb[l - 1][ln.rb][n0 + 32 * t] += sum;
       }
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
       __builtin_amdgcn_s_barrier();  // every wave has read the image for the last time
 #pragma unroll
-      for (int t = 0; t < NT; ++t)
-#pragma unroll
-        for (int r = 0; r < 16; ++r)
-          sm.img[(rb * 32 + acc_row(r, lh)) * S::ld + n0 + t * 32] = pz[t][r];
+      for (int t = 0; t < NT; ++t) store_acc<S>(sm.img, ln, pz[t], t);
       if (l - 1 >= 1) {  // dz_{l-1} feeds the weight gradient of layer l-1
         pend_l = l - 1, pend_m0 = m0;
       }
@@ -944,7 +884,7 @@ int launch_backward(const BwdArgs& a, hipStream_t st) {
 }
 
 template <int H>
-int launch_wgrad(const WgradArgs& g, float* d_weight, hipStream_t st, int ld = H) {
+int launch_wgrad(const WgradArgs& g, float* d_weight, hipStream_t st, int ld) {
   using W = WgradShape<H>;
   const int wb = wgrad_blocks(g.n);
   hipLaunchKernelGGL((siren_wgrad_kernel<W>), dim3(wb), dim3(kThreads), 0, st, g);
@@ -958,12 +898,7 @@ int forward_any(int hidden, const ChainArgs& a, int mode, hipStream_t st) {
   if (options().siren_rows && rows_supported(hidden, a.n_sine) &&
       (mode != 2 || rows_backward_supported(hidden, a.n_sine, a.dim_in, 1)))
     return forward_rows(a, mode, st);
-  switch (hidden) {
-    case 32: return launch_forward<32>(a, mode, st);
-    case 64: return launch_forward<64>(a, mode, st);
-    case 128: return launch_forward<128>(a, mode, st);
-    default: return launch_forward<256>(a, mode, st);
-  }
+  return dispatch_hidden(hidden, [&](auto h) { return launch_forward<decltype(h)::value>(a, mode, st); });
 }
 
 // loss-mode slabs -> head weight / bias gradient, last sine layer's bias gradient, loss
@@ -1003,21 +938,7 @@ __global__ __launch_bounds__(256) void siren_fwd_reduce_kernel(const FwdReduceAr
 }
 
 int backward_any(int hidden, const BwdArgs& a, hipStream_t st) {
-  switch (hidden) {
-    case 32: return launch_backward<32>(a, st);
-    case 64: return launch_backward<64>(a, st);
-    case 128: return launch_backward<128>(a, st);
-    default: return launch_backward<256>(a, st);
-  }
-}
-
-int wgrad_any(int hidden, const WgradArgs& g, float* d_weight, hipStream_t st) {
-  switch (hidden) {
-    case 32: return launch_wgrad<32>(g, d_weight, st);
-    case 64: return launch_wgrad<64>(g, d_weight, st);
-    case 128: return launch_wgrad<128>(g, d_weight, st);
-    default: return launch_wgrad<256>(g, d_weight, st);
-  }
+  return dispatch_hidden(hidden, [&](auto h) { return launch_backward<decltype(h)::value>(a, st); });
 }
 
 }  // namespace
@@ -1037,12 +958,7 @@ int split_weights_ld(const float* const* w, int count, int hidden, int ld, bool 
 }
 
 int wgrad_any_ld(int hidden, const WgradArgs& g, float* d_weight, int ld, hipStream_t st) {
-  switch (hidden) {
-    case 32: return launch_wgrad<32>(g, d_weight, st, ld);
-    case 64: return launch_wgrad<64>(g, d_weight, st, ld);
-    case 128: return launch_wgrad<128>(g, d_weight, st, ld);
-    default: return launch_wgrad<256>(g, d_weight, st, ld);
-  }
+  return dispatch_hidden(hidden, [&](auto h) { return launch_wgrad<decltype(h)::value>(g, d_weight, st, ld); });
 }
 
 int64_t wgrad_slab_floats(int64_t n, int hidden) {
@@ -1056,7 +972,6 @@ using namespace mri;
 namespace {
 // The (n, hidden) tensors leave and return in 16-byte pieces: the rows kernels (hidden 256) store act / deriv / dz_last
 // four floats a lane, the weight-gradient kernels stream act and dz into LDS sixteen bytes a lane.
-bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 constexpr const char* kActAlignment = "act / deriv buffers must be 16-byte aligned (layer %d)";
 }  // namespace
 
@@ -1078,7 +993,7 @@ extern "C" int mri_siren_forward(const float* x, int64_t n, int32_t dim_in, int3
   MRI_REQUIRE(x && weight && bias && y, "NULL pointer");
   const int64_t need = split_region_bytes(hidden, n_sine_layers);
   MRI_REQUIRE(need == 0 || (workspace && workspace_bytes >= need &&
-                            (reinterpret_cast<uintptr_t>(workspace) & 15) == 0),
+                            aligned_to(workspace, 16)),
               "SIREN forward needs a 16-byte aligned workspace of %lld bytes "
               "(mri_siren_forward_workspace_bytes)", (long long)need);
   MRI_REQUIRE((act == nullptr) == (deriv == nullptr), "act and deriv go together");
@@ -1087,14 +1002,14 @@ extern "C" int mri_siren_forward(const float* x, int64_t n, int32_t dim_in, int3
   a.w0_first = w0_first, a.w0 = w0, a.y = y;
   for (int l = 0; l <= n_sine_layers; ++l) {
     MRI_REQUIRE(weight[l] && bias[l], "NULL parameter pointer (layer %d)", l);
-    MRI_REQUIRE((reinterpret_cast<uintptr_t>(weight[l]) & 15) == 0,
+    MRI_REQUIRE(aligned_to(weight[l], 16),
                 "weights must be 16-byte aligned (layer %d)", l);
     a.w[l] = weight[l], a.b[l] = bias[l];
   }
   if (act)
     for (int l = 0; l < n_sine_layers; ++l) {
       MRI_REQUIRE(act[l] && deriv[l], "NULL activation buffer (layer %d)", l);
-      MRI_REQUIRE(aligned16(act[l]) && aligned16(deriv[l]), kActAlignment, l);
+      MRI_REQUIRE(aligned_to(act[l], 16) && aligned_to(deriv[l], 16), kActAlignment, l);
       a.act[l] = act[l], a.deriv[l] = deriv[l];
     }
   a.wsplit = static_cast<const char*>(workspace);
@@ -1156,7 +1071,7 @@ extern "C" int mri_siren_forward_loss(const float* x, const float* target, int64
                   d_b_head && d_b_last && loss_out, "NULL pointer");
   const int blocks = chain_blocks(hidden, n);
   const int64_t need = mri_siren_backward_workspace_bytes(n, hidden, n_sine_layers);
-  MRI_REQUIRE(workspace && workspace_bytes >= need && (reinterpret_cast<uintptr_t>(workspace) & 15) == 0,
+  MRI_REQUIRE(workspace && workspace_bytes >= need && aligned_to(workspace, 16),
               "SIREN forward with loss needs a 16-byte aligned workspace of %lld bytes "
               "(mri_siren_backward_workspace_bytes)", (long long)need);
   char* const wsplit = static_cast<char*>(workspace) + slab_region_bytes(n, hidden, n_sine_layers);
@@ -1169,16 +1084,16 @@ extern "C" int mri_siren_forward_loss(const float* x, const float* target, int64
   a.inv_n = (float)(1.0 / (double)n_total);
   for (int l = 0; l <= n_sine_layers; ++l) {
     MRI_REQUIRE(weight[l] && bias[l], "NULL parameter pointer (layer %d)", l);
-    MRI_REQUIRE((reinterpret_cast<uintptr_t>(weight[l]) & 15) == 0,
+    MRI_REQUIRE(aligned_to(weight[l], 16),
                 "weights must be 16-byte aligned (layer %d)", l);
     a.w[l] = weight[l], a.b[l] = bias[l];
   }
   for (int l = 0; l + 1 < n_sine_layers; ++l) {  // the last sine layer's a / w0 cos stay on chip
     MRI_REQUIRE(act[l] && deriv[l], "NULL activation buffer (layer %d)", l);
-    MRI_REQUIRE(aligned16(act[l]) && aligned16(deriv[l]), kActAlignment, l);
+    MRI_REQUIRE(aligned_to(act[l], 16) && aligned_to(deriv[l], 16), kActAlignment, l);
     a.act[l] = act[l], a.deriv[l] = deriv[l];
   }
-  MRI_REQUIRE(aligned16(dz_last), "dz_last must be 16-byte aligned");
+  MRI_REQUIRE(aligned_to(dz_last, 16), "dz_last must be 16-byte aligned");
   hipStream_t st = (hipStream_t)stream;
   a.wsplit = wsplit;
   remember_loss_call(LossCall{workspace, dz_last, n, hidden, n_sine_layers,
@@ -1230,7 +1145,7 @@ extern "C" int mri_siren_backward(const float* x, const float* dy, int64_t n, in
               "NULL pointer");
   const int L = n_sine_layers;
   const int64_t need = mri_siren_backward_workspace_bytes(n, hidden, L);
-  MRI_REQUIRE(workspace && workspace_bytes >= need && (reinterpret_cast<uintptr_t>(workspace) & 15) == 0,
+  MRI_REQUIRE(workspace && workspace_bytes >= need && aligned_to(workspace, 16),
               "SIREN backward needs a 16-byte aligned workspace of %lld bytes "
               "(mri_siren_backward_workspace_bytes)", (long long)need);
   hipStream_t st = (hipStream_t)stream;
@@ -1241,15 +1156,15 @@ extern "C" int mri_siren_backward(const float* x, const float* dy, int64_t n, in
   a.dy_ws = reinterpret_cast<const float*>(static_cast<const char*>(workspace) + rows_dy_offset(n, hidden, L));
   for (int l = 0; l <= L; ++l) {
     MRI_REQUIRE(weight[l] && d_weight[l] && d_bias[l], "NULL parameter / gradient pointer (layer %d)", l);
-    MRI_REQUIRE((reinterpret_cast<uintptr_t>(weight[l]) & 15) == 0, "weights must be 16-byte aligned");
+    MRI_REQUIRE(aligned_to(weight[l], 16), "weights must be 16-byte aligned");
     a.w[l] = weight[l];
   }
   for (int l = 0; l < L; ++l) {
     const bool on_chip = head_done && l == L - 1;  // the loss-mode forward never stored these
     MRI_REQUIRE((on_chip || (act[l] && deriv[l])) && (l == 0 || dz[l]),
                 "NULL activation buffer (layer %d)", l);
-    MRI_REQUIRE(on_chip || (aligned16(act[l]) && aligned16(deriv[l])), kActAlignment, l);
-    MRI_REQUIRE(l == 0 || aligned16(dz[l]), "dz buffers must be 16-byte aligned (layer %d)", l);
+    MRI_REQUIRE(on_chip || (aligned_to(act[l], 16) && aligned_to(deriv[l], 16)), kActAlignment, l);
+    MRI_REQUIRE(l == 0 || aligned_to(dz[l], 16), "dz buffers must be 16-byte aligned (layer %d)", l);
     a.deriv[l] = on_chip ? nullptr : deriv[l];
     a.dz[l] = dz[l];
   }
@@ -1279,7 +1194,7 @@ extern "C" int mri_siren_backward(const float* x, const float* dy, int64_t n, in
   for (int l = L - 1; l >= 1; --l) {  // dW_l = dz_l^T a_{l-1}
     WgradArgs g{};
     g.dz = dz[l], g.act = act[l - 1], g.n = n, g.partial = static_cast<float*>(workspace);
-    if (int rc = wgrad_any(hidden, g, d_weight[l], st)) return rc;
+    if (int rc = wgrad_any_ld(hidden, g, d_weight[l], hidden, st)) return rc;
   }
   return MRI_OK;
 }

@@ -7,13 +7,13 @@
 //   T_l^d = (w_l cos(w_l z_l)) (.) (T_{l-1}^d W_l^T)       the product of the value row, on more rows, without bias
 //   dy / dx_d = T_{L-1}^d . w_head
 //
-// so the tile loop of siren_forward_kernel (siren_chain.hip, inference mode) serves as it is when the activation
-// image holds, per POINT, four consecutive rows at a 4-aligned position: the value row and the tangent rows of x_0,
+// so the LDS-image tile loop (chain_tile.h), walked as siren_forward_kernel walks it in inference mode, serves when
+// the activation image holds, per POINT, four consecutive rows at a 4-aligned position: the value row and the tangent rows of x_0,
 // x_1, x_2 (rows of absent axes and of points beyond n are zero and are never stored).  The accumulator layout of the
 // 32x32 MFMA (acc_row) puts rows 4 q .. 4 q + 3 of a wave's row block into registers 4 q .. 4 q + 3 of ONE lane: the
 // epilogue, where the tangent rows need the value row's w cos(.), is lane-local -- no shuffles, no LDS traffic --
 // and only one register in four pays a sincos.  The weight chunks (LDS-DMA, double buffered), the bf16x3 products
-// and the split weights are those of the forward kernel (siren_chain.h); nothing (n, H)-sized reaches memory: the
+// and the split weights are those of the forward kernel (chain_tile.h, siren_chain.h); nothing (n, H)-sized reaches memory: the
 // call reads n dim_in floats and writes n (1 + dim_in).
 //
 // dim_in = 4 (a dynamic sequence: x, y, z, t) takes the EIGHT-slot instantiation of the same kernel body: a point's
@@ -41,27 +41,16 @@ using namespace chain;
 constexpr int kGradMaxIn = 4;   // axes the eight-slot form holds (the four-slot form: 3)
 constexpr int kGradMaxBlocks = 256;
 
-// Geometry for hidden width H: that of the forward kernel (a wave owns a 32 x CT tile of the layer output, the 8
-// waves are RB row blocks x CB column blocks), the rows counted in points of SL image rows: 4 (value, d/dx_0,
-// d/dx_1, d/dx_2) for dim_in <= 3, 8 (value, d/dx_0 .. d/dx_2 | value, d/dx_3, 0, 0) for dim_in = 4.
+// Geometry for hidden width H: that of the forward kernel (image rows of a tile: 64, 128, 256, 256 for H = 256 .. 32),
+// the rows counted in points of SL image rows: 4 (value, d/dx_0, d/dx_1, d/dx_2) for dim_in <= 3, 8 (value, d/dx_0 ..
+// d/dx_2 | value, d/dx_3, 0, 0) for dim_in = 4.  Points of a tile: 16, 32, 64, 64 (8 slots: 8, 16, 32, 32).
 template <int HH, int SL>
-struct GradShape {
-  static constexpr int H = HH;
-  static constexpr int slots = SL;
-  static constexpr int max_in = SL == 4 ? 3 : 4;    // axes the slots hold
-  static constexpr int CT = H < 64 ? H : 64;
-  static constexpr int NT = CT / 32;
-  static constexpr int CB = H / CT, RB = 8 / CB;
-  static constexpr int rows = 32 * RB;              // image rows of a tile: 64, 128, 256, 256
-  static constexpr int points = rows / SL;          // points of a tile: 16, 32, 64, 64 (8 slots: 8, 16, 32, 32)
-  static constexpr int ld = H + 4;                  // image row stride: rows 4 banks apart (mod 64)
-  static constexpr int chunks = H / kKc;
-  static constexpr int chunk_bytes = 3 * H * 32;
-  static constexpr int groups = kThreads / H;       // point groups of the first layer's (column, group) mapping
-  static constexpr int ppt = points / groups;       // points per thread there: 8, 8, 8, 4 (8 slots: 4, 4, 4, 2)
+struct GradShape : TileShape<HH, 64, SL> {
+  using T = TileShape<HH, 64, SL>;
+  static constexpr int max_in = SL == 4 ? 3 : 4;        // axes the slots hold
+  static constexpr int ppt = T::points / T::groups;     // points per thread of the first layer: 8, 8, 8, 4 (8 slots: 4, 4, 4, 2)
   static_assert(SL == 4 || SL == 8, "image rows per point");
-  static_assert(H == 32 || H == 64 || H == 128 || H == 256, "hidden width");
-  static_assert(ppt % 2 == 0 && ppt * groups == points, "first-layer mapping");
+  static_assert(ppt % 2 == 0 && ppt * T::groups == T::points, "first-layer mapping");
 };
 
 template <class S>
@@ -89,38 +78,32 @@ template <class S>
 __global__ __launch_bounds__(kThreads) void siren_gradient_kernel(const GradArgs a) {
   __shared__ GradSmem<S> sm;
   constexpr int H = S::H, NT = S::NT, kSlots = S::slots, kMaxIn = S::max_in;
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int l31 = lane & 31, lh = lane >> 5;
-  const int rb = wave / S::CB, cb = wave % S::CB;
+  const Lanes<S> ln;
+  const int tid = ln.tid;
   const int n_mm = a.n_sine - 1;  // H x H layers
 
   // ---- small resident parameters ------------------------------------------------------------
-  for (int l = 0; l < a.n_sine; ++l)
-    for (int e = tid; e < H; e += kThreads) sm.bias[l][e] = a.b[l][e];
-  for (int e = tid; e < H; e += kThreads) sm.w_last[e] = a.w[a.n_sine][e];
+  for (int l = 0; l < a.n_sine; ++l) load_vector<H>(sm.bias[l], a.b[l], tid);
+  load_vector<H>(sm.w_last, a.w[a.n_sine], tid);
   const float b_last = a.b[a.n_sine][0];
 
   const int64_t tiles = (a.n + S::points - 1) / S::points;
-  const float* a_row = sm.img + (rb * 32 + l31) * S::ld + 4 * lh;
-  const int n0 = cb * S::CT + l31;  // column of tile 0; tile t: + 32 t
+  const float* a_row = sm.img + ln.fragment_offset();
   int boff[NT];
-#pragma unroll
-  for (int t = 0; t < NT; ++t) boff[t] = 32 * (n0 + 32 * t) + 16 * (lh ^ (((n0 + 32 * t) >> 3) & 1));
+  ln.weight_offsets(boff);
 
-  // chunk stream: chunk s (layer 1 + (s / chunks) % n_mm) lives in wbuf[s & 1]
-  int s = 0;
-  if (n_mm > 0 && (int64_t)blockIdx.x < tiles) issue_chunk<S>(a.wsplit, 0, sm.wbuf[0], wave, lane);
+  ChunkStream<S, 1> stream(n_mm, tiles);
+  auto issue = [&](int layer, int kc, int buf) {  // the matrix of layer `layer` (1 .. n_mm), chunk kc
+    issue_chunk<S>(a.wsplit + (layer - 1) * split_matrix_bytes(H), kc, sm.wbuf[buf], ln.wave, ln.lane);
+  };
+  stream.prime(issue);
 
   for (int64_t tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
     const int64_t p0 = tile * S::points;  // first point of the tile
     // ---- coordinates -> LDS ---------------------------------------------------------------------
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();  // previous tile is done with img / xs
-    for (int e = tid; e < S::points * kSlots; e += kThreads) {
-      const int p = e / kSlots, d = e % kSlots;
-      sm.xs[e] = (d < a.dim_in && p0 + p < a.n) ? a.x[(p0 + p) * a.dim_in + d] : 0.f;
-    }
+    stage_coords<kSlots>(sm.xs, a.x, p0, S::points, a.n, a.dim_in, tid);
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();
     // ---- first layer on the VALU: thread <-> (column, group of points) --------------------------
@@ -163,7 +146,7 @@ __global__ __launch_bounds__(kThreads) void siren_gradient_kernel(const GradArgs
         }
       }
     }
-    // ---- H x H layers: the forward kernel's loop ------------------------------------------------
+    // ---- H x H layers --------------------------------------------------------------------------
     for (int l = 1; l <= n_mm; ++l) {
       f32x16 acc[NT];
 #pragma unroll
@@ -172,20 +155,10 @@ __global__ __launch_bounds__(kThreads) void siren_gradient_kernel(const GradArgs
         for (int r = 0; r < 16; ++r) acc[t][r] = 0.f;
       x3::Frag fa;
 #pragma unroll
-      for (int kc = 0; kc < S::chunks; ++kc, ++s) {
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // chunk s has landed (this wave's pieces)
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        __builtin_amdgcn_s_barrier();  // ... for every wave, and wbuf[(s + 1) & 1] is free
-        {
-          const bool more_k = kc + 1 < S::chunks;
-          const int nl = more_k ? l : (l < n_mm ? l + 1 : 1);
-          if (more_k || l < n_mm || tile + gridDim.x < tiles)
-            issue_chunk<S>(a.wsplit + (nl - 1) * split_matrix_bytes(H), more_k ? kc + 1 : 0,
-                           sm.wbuf[(s + 1) & 1], wave, lane);
-        }
-        __builtin_amdgcn_sched_barrier(0);
-        if (kc == 0) fa = first_fragment(a_row);  // (the barrier above completed the image)
-        mma_chunk<NT, H>(acc, fa, kc + 1 < S::chunks ? a_row + (kc + 1) * kKc : nullptr, sm.wbuf[s & 1], boff);
+      for (int kc = 0; kc < S::chunks; ++kc, stream.consumed()) {
+        stream.advance(tile, l, kc, issue);
+        if (kc == 0) fa = first_fragment(a_row);  // (the stream's barrier completed the image)
+        mma_step<S>(acc, fa, a_row, kc, sm.wbuf[stream.buffer()], boff);
       }
       // ---- epilogue: registers 4 q .. 4 q + 3 are one point's value and tangent rows (8 slots: of either half
       //      of the point, the value row being there twice) -----------------------------------------------
@@ -193,7 +166,7 @@ __global__ __launch_bounds__(kThreads) void siren_gradient_kernel(const GradArgs
       float pa[NT][16];
 #pragma unroll
       for (int t = 0; t < NT; ++t) {
-        const float bj = sm.bias[l][n0 + 32 * t];
+        const float bj = sm.bias[l][ln.n0 + 32 * t];
 #pragma unroll
         for (int q = 0; q < 4; q += 2) {
           float s0, c0, s1, c1;
@@ -210,34 +183,23 @@ __global__ __launch_bounds__(kThreads) void siren_gradient_kernel(const GradArgs
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
       __builtin_amdgcn_s_barrier();  // every wave has read the image for the last time
 #pragma unroll
-      for (int t = 0; t < NT; ++t)
-#pragma unroll
-        for (int r = 0; r < 16; ++r)
-          sm.img[(rb * 32 + acc_row(r, lh)) * S::ld + n0 + t * 32] = pa[t][r];
+      for (int t = 0; t < NT; ++t) store_acc<S>(sm.img, ln, pa[t], t);
     }
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();  // image complete
     // ---- head: image row . w_head, one wave per row; slot 0 -> y (+ bias), slot 1 + d -> dydx[:, d]; of the
     //      upper four of 8 slots only slot 5 -> dydx[:, 3] is stored ------------------------------------------
     {
-      constexpr int kPer = H >= 64 ? H / 64 : 1;  // elements per lane (H = 32: half the lanes)
-      float wv[kPer];
-#pragma unroll
-      for (int j = 0; j < kPer; ++j) wv[j] = lane + 64 * j < H ? sm.w_last[lane + 64 * j] : 0.f;
+      const HeadDot<S> head(sm.w_last, ln.lane);
 #pragma unroll 4
       for (int i = 0; i < S::rows / 8; ++i) {
-        const int row = wave * (S::rows / 8) + i;  // wave-uniform
+        const int row = ln.wave * (S::rows / 8) + i;  // wave-uniform
         const int slot = row % kSlots;
         const int64_t p = p0 + row / kSlots;
         const int axis = slot < 4 ? slot - 1 : (slot == 5 ? 3 : kMaxIn);  // wave-uniform; -1: the value
         if (axis >= a.dim_in || p >= a.n) continue;
-        float acc1 = 0.f;
-#pragma unroll
-        for (int j = 0; j < kPer; ++j)
-          if (lane + 64 * j < H) acc1 += sm.img[row * S::ld + lane + 64 * j] * wv[j];
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) acc1 += __shfl_down(acc1, off, 64);
-        if (lane == 0) {
+        const float acc1 = head(sm.img + row * S::ld);
+        if (ln.lane == 0) {
           if (slot == 0)
             a.y[p] = acc1 + b_last;
           else
@@ -296,18 +258,12 @@ extern "C" int mri_siren_gradient(const float* x, int64_t n, int32_t dim_in, int
               kGradMaxIn);
   MRI_REQUIRE(n_sine_layers >= 1 && n_sine_layers <= kMaxSine,
               "SIREN gradient: n_sine_layers = %d is not supported (1 .. %d)", n_sine_layers, kMaxSine);
-  MRI_REQUIRE(n >= 0 && n < (1ll << 31), "n = %lld out of range", (long long)n);
+  if (int rc = check_gradient_io(x, n, y, dydx)) return rc;
   if (n == 0) return MRI_OK;
-  MRI_REQUIRE(x, "x is NULL");
   MRI_REQUIRE(weight, "weight is NULL");
   MRI_REQUIRE(bias, "bias is NULL");
-  MRI_REQUIRE(y, "y is NULL");
-  MRI_REQUIRE(dydx, "dydx is NULL");
-  MRI_REQUIRE((reinterpret_cast<uintptr_t>(x) & 3) == 0, "x must be 4-byte aligned");
-  MRI_REQUIRE((reinterpret_cast<uintptr_t>(y) & 3) == 0, "y must be 4-byte aligned");
-  MRI_REQUIRE((reinterpret_cast<uintptr_t>(dydx) & 3) == 0, "dydx must be 4-byte aligned");
   const int64_t need = gradient_split_bytes(hidden, n_sine_layers);
-  MRI_REQUIRE(need == 0 || (workspace && workspace_bytes >= need && (reinterpret_cast<uintptr_t>(workspace) & 15) == 0),
+  MRI_REQUIRE(need == 0 || (workspace && workspace_bytes >= need && aligned_to(workspace, 16)),
               "workspace: the SIREN gradient needs %lld bytes, 16-byte aligned (mri_siren_gradient_workspace_bytes)",
               (long long)need);
   GradArgs a{};
@@ -316,7 +272,7 @@ extern "C" int mri_siren_gradient(const float* x, int64_t n, int32_t dim_in, int
   for (int l = 0; l <= n_sine_layers; ++l) {
     MRI_REQUIRE(weight[l], "weight[%d] is NULL", l);
     MRI_REQUIRE(bias[l], "bias[%d] is NULL", l);
-    MRI_REQUIRE((reinterpret_cast<uintptr_t>(weight[l]) & 15) == 0, "weight[%d] must be 16-byte aligned", l);
+    MRI_REQUIRE(aligned_to(weight[l], 16), "weight[%d] must be 16-byte aligned", l);
     a.w[l] = weight[l], a.b[l] = bias[l];
   }
   a.wsplit = static_cast<const char*>(workspace);
@@ -324,10 +280,5 @@ extern "C" int mri_siren_gradient(const float* x, int64_t n, int32_t dim_in, int
   if (int rc = split_weights_ld(weight + 1, n_sine_layers - 1, hidden, hidden, false, static_cast<char*>(workspace),
                                 split_matrix_bytes(hidden), st))
     return rc;
-  switch (hidden) {
-    case 32: return launch_gradient<32>(a, st);
-    case 64: return launch_gradient<64>(a, st);
-    case 128: return launch_gradient<128>(a, st);
-    default: return launch_gradient<256>(a, st);
-  }
+  return dispatch_hidden(hidden, [&](auto h) { return launch_gradient<decltype(h)::value>(a, st); });
 }
