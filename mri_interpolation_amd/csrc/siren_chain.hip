@@ -783,23 +783,37 @@ __global__ __launch_bounds__(kThreads) void siren_wgrad_kernel(const WgradArgs g
 }
 
 // dst[e] += sum over slabs of partial[slab][e], fixed order; the slab is a row-major matrix of `cols` columns and
-// dst one of row stride `ld` (ld > cols: the H x H block in front of a modulator layer's (H, H + dim_in) weight)
+// dst one of row stride `ld` (ld > cols: the H x H block in front of a modulator layer's (H, H + dim_in) weight).
+// There are 256 x wgrad_split slabs (2048 at H = 32, 512 at H = 64) of signed terms, and one float32 chain that long
+// moved an H x H gradient by up to 3.7e-6 of its largest element when the same rows were cut into two launches
+// (tests/test_gpu_tile_loop.py).  So eight slabs meet in a float32 tree (three roundings deep) and the trees' sums
+// are added in float64.  A thread waits for a round of loads before it issues the next, and what it computes behind
+// the last load of a round is exposed: sixteen loads a round, so that the longer tail comes half as often.
+__device__ __forceinline__ float sum8(const float* v) {
+  return ((v[0] + v[1]) + (v[2] + v[3])) + ((v[4] + v[5]) + (v[6] + v[7]));
+}
+
 __global__ __launch_bounds__(256) void slab_sum_kernel(const float* __restrict__ partial, int slabs,
                                                        int count, float* __restrict__ dst, int cols, int ld) {
   const int e = blockIdx.x * 256 + threadIdx.x;
   if (e >= count) return;
   const float* p = partial + e;
-  float sum = 0.f;
+  double sum = 0.0;
   int b = 0;
+  for (; b + 16 <= slabs; b += 16) {
+    float v[16];
+#pragma unroll
+    for (int j = 0; j < 16; ++j) v[j] = p[(int64_t)(b + j) * count];
+    sum += (double)sum8(v) + (double)sum8(v + 8);
+  }
   for (; b + 8 <= slabs; b += 8) {
     float v[8];
 #pragma unroll
     for (int j = 0; j < 8; ++j) v[j] = p[(int64_t)(b + j) * count];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) sum += v[j];
+    sum += (double)sum8(v);
   }
-  for (; b < slabs; ++b) sum += p[(int64_t)b * count];
-  dst[ld == cols ? e : (e / cols) * ld + e % cols] += sum;
+  for (; b < slabs; ++b) sum += (double)p[(int64_t)b * count];
+  dst[ld == cols ? e : (e / cols) * ld + e % cols] += (float)sum;
 }
 
 // Three-term split of the H x H weights into the chunk-major planes issue_chunk streams (layout:
