@@ -2,6 +2,7 @@
 #pragma once
 #include "common.h"
 #include "hashgrid_common.h"
+#include "slab.h"
 
 namespace mri {
 
@@ -13,7 +14,7 @@ struct FusedArgs {
   const float* w3; const float* b3;   // (1, H), (1)
   float* y;            // (n) predictions, optional
   float* dx;           // (k_in, n) feature-major, optional
-  float* partial;      // [gridDim.x][slab] partial gradients + loss
+  float* partial;      // [gridDim.x][MlpSlab] partial gradients + loss
   int64_t n;
   int64_t ld;          // leading dimension of x and dx (elements between feature rows), >= n
   int k_in;
@@ -41,9 +42,6 @@ struct EncodeArgs {
   int n_levels = 0;
   int dim = 0;                    // 0: features come from FusedArgs::x
 };
-
-// slab layout (floats): dW1 [H*k_in] | db1 [H] | dW2 [H*H] | db2 [H] | dW3 [H] | db3 [1] | loss [1]
-__host__ __device__ inline int slab_floats(int H, int k_in) { return H * k_in + H + H * H + H + H + 2; }
 
 // mlp_x3.hip: k_in <= 32 -> 128 -> 128 -> 1 and -> 64 -> 64 -> 1 on the bf16 matrix pipe (three-term split operands), one
 // 512-thread workgroup per CU, one slab per workgroup (train).  `blocks` <= x3_max_blocks(n).

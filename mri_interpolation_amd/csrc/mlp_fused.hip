@@ -400,13 +400,14 @@ __global__ __launch_bounds__(kThreads, 2) void tiny_mlp_kernel(const FusedArgs a
   flush_dx();
 
   // ---- write this workgroup's partial gradients (plain stores, summed by reduce kernel) ----
-  float* slab = a.partial + (int64_t)blockIdx.x * slab_floats(H, a.k_in);
-  float* p_w1 = slab;
-  float* p_b1 = p_w1 + H * a.k_in;
-  float* p_w2 = p_b1 + H;
-  float* p_b2 = p_w2 + H * H;
-  float* p_w3 = p_b2 + H;
-  float* p_b3 = p_w3 + H;
+  const MlpSlab lay{H, a.k_in};
+  float* slab = a.partial + (int64_t)blockIdx.x * lay.floats();
+  float* p_w1 = lay.w1(slab);
+  float* p_b1 = lay.b1(slab);
+  float* p_w2 = lay.w2(slab);
+  float* p_b2 = lay.b2(slab);
+  float* p_w3 = lay.w3(slab);
+  float* p_b3 = lay.b3(slab);
   __syncthreads();
   // dW2: wave's tiles
 #pragma unroll
@@ -460,7 +461,7 @@ __global__ __launch_bounds__(kThreads, 2) void tiny_mlp_kernel(const FusedArgs a
       l += red[kTile + c];
     }
     p_b3[0] = s;
-    p_b3[1] = l * a.inv_n;
+    *lay.loss(slab) = l * a.inv_n;
   }
 }
 
@@ -834,13 +835,14 @@ __global__ __launch_bounds__(2 * kTeamThreads) void tiny_mlp_team_kernel(const F
     PROF_END(threadIdx.x >> 6)
     return;
   }
-  float* slab = a.partial + (int64_t)blockIdx.x * slab_floats(H, a.k_in);
-  float* p_w1 = slab;
-  float* p_b1 = p_w1 + H * a.k_in;
-  float* p_w2 = p_b1 + H;
-  float* p_b2 = p_w2 + H * H;
-  float* p_w3 = p_b2 + H;
-  float* p_b3 = p_w3 + H;
+  const MlpSlab lay{H, a.k_in};
+  float* slab = a.partial + (int64_t)blockIdx.x * lay.floats();
+  float* p_w1 = lay.w1(slab);
+  float* p_b1 = lay.b1(slab);
+  float* p_w2 = lay.w2(slab);
+  float* p_b2 = lay.b2(slab);
+  float* p_w3 = lay.w3(slab);
+  float* p_b3 = lay.b3(slab);
 #pragma unroll
   for (int tj = 0; tj < 4; ++tj)
 #pragma unroll
@@ -873,52 +875,10 @@ __global__ __launch_bounds__(2 * kTeamThreads) void tiny_mlp_team_kernel(const F
       }
     }
     p_b3[0] = sb;
-    p_b3[1] = sl * a.inv_n;
+    *lay.loss(slab) = sl * a.inv_n;
   }
   PROF_MARK(21)  // epilogue: team merge + slab
   PROF_END(threadIdx.x >> 6)
-}
-
-// Sum the per-workgroup slabs in a fixed order into the gradient tensors (accumulating).
-struct ReduceArgs {
-  const float* partial;
-  int slabs, slab;
-  int n_seg;
-  int overwrite;
-  int seg_begin[8];   // offsets inside a slab
-  int seg_len[8];
-  float* dst[8];
-};
-
-__global__ __launch_bounds__(256) void slab_reduce_kernel(const ReduceArgs r) {
-  // 64 elements per workgroup; 4 thread groups each sum a quarter of the slabs (8 loads in
-  // flight), then the quarters are added in a fixed order -> same bits every run.
-  __shared__ float quarter[4][64];
-  const int e = blockIdx.x * 64 + (threadIdx.x & 63), grp = threadIdx.x >> 6;
-  const int per = (r.slabs + 3) / 4;
-  const int b_lo = grp * per, b_hi = min(r.slabs, b_lo + per);
-  float s = 0.f;
-  if (e < r.slab) {
-    const float* p = r.partial + e;
-    int b = b_lo;
-    for (; b + 8 <= b_hi; b += 8) {
-      float v[8];
-#pragma unroll
-      for (int j = 0; j < 8; ++j) v[j] = p[(int64_t)(b + j) * r.slab];
-#pragma unroll
-      for (int j = 0; j < 8; ++j) s += v[j];
-    }
-    for (; b < b_hi; ++b) s += p[(int64_t)b * r.slab];
-  }
-  quarter[grp][threadIdx.x & 63] = s;
-  __syncthreads();
-  if (grp != 0 || e >= r.slab) return;
-  s = ((quarter[0][threadIdx.x] + quarter[1][threadIdx.x]) + quarter[2][threadIdx.x]) +
-      quarter[3][threadIdx.x];
-#pragma unroll
-  for (int g = 0; g < 8; ++g)
-    if (g < r.n_seg && e >= r.seg_begin[g] && e < r.seg_begin[g] + r.seg_len[g])
-      r.dst[g][e - r.seg_begin[g]] = r.overwrite ? s : r.dst[g][e - r.seg_begin[g]] + s;
 }
 
 template <int H, int KP>
@@ -984,7 +944,7 @@ extern "C" int mri_tiny_mlp_supported(int32_t k_in, int32_t hidden, int32_t dim_
 
 extern "C" int64_t mri_tiny_mlp_workspace_bytes(int32_t k_in, int32_t hidden, int64_t n) {
   if (!supported(k_in, hidden, 1)) return -1;
-  return (int64_t)slab_count(hidden, k_in, std::max<int64_t>(n, 1)) * slab_floats(hidden, k_in) * 4;
+  return (int64_t)slab_count(hidden, k_in, std::max<int64_t>(n, 1)) * MlpSlab{hidden, k_in}.floats() * 4;
 }
 
 extern "C" int mri_tiny_mlp_forward(const float* x, int64_t n, int32_t k_in, int32_t hidden,
@@ -1009,6 +969,31 @@ struct Overlap {
   int* status = nullptr;
 };
 
+struct MlpGrads {
+  float *w1, *b1, *w2, *b2, *w3, *b3, *loss;
+};
+
+// What every training entry point does before and after its own kernel launch.
+// Before: the gradient pointers, the workspace check (what mri_tiny_mlp_workspace_bytes reports, for every call alike: the
+// 64-wide f32-MFMA kernel's slab count may exceed the launched kernel's), the slab pointer and the scales of `a`.
+static int prepare_training(FusedArgs& a, int hidden, int64_t n_total, float grad_divisor, const MlpGrads& g,
+                            void* workspace, int64_t workspace_bytes) {
+  MRI_REQUIRE(g.w1 && g.b1 && g.w2 && g.b2 && g.w3 && g.b3 && g.loss, "NULL gradient pointer");
+  const int64_t need = (int64_t)slab_count(hidden, a.k_in, a.n) * MlpSlab{hidden, a.k_in}.floats() * 4;
+  MRI_REQUIRE(workspace && workspace_bytes >= need,
+              "tiny MLP needs a workspace of %lld bytes (mri_tiny_mlp_workspace_bytes)", (long long)need);
+  a.partial = static_cast<float*>(workspace);
+  a.grad_scale = (float)(2.0 / ((double)n_total * (double)grad_divisor));
+  a.inv_n = (float)(1.0 / (double)n_total);
+  return MRI_OK;
+}
+// After: the slabs of the `blocks` workgroups the kernel ran on, added into (or written over) the gradients and the loss.
+static int reduce_training(const FusedArgs& a, int hidden, int blocks, int overwrite, const MlpGrads& g, hipStream_t st) {
+  const MlpSlab lay{hidden, a.k_in};
+  return reduce_slabs<4>(a.partial, blocks, lay.floats(),
+                         segments(lay, overwrite, g.w1, g.b1, g.w2, g.b2, g.w3, g.b3, g.loss), st);
+}
+
 static int tiny_mlp_train_impl(int overwrite, int64_t ld, int64_t n_total, const float* x, const float* target, int64_t n, int32_t k_in,
                                   int32_t hidden, const float* w1, const float* b1,
                                   const float* w2, const float* b2, const float* w3,
@@ -1024,39 +1009,22 @@ static int tiny_mlp_train_impl(int overwrite, int64_t ld, int64_t n_total, const
               (long long)n, (long long)ld, (long long)n_total);
   if (n == 0) return MRI_OK;
   MRI_REQUIRE(x && target && w1 && b1 && w2 && b2 && w3 && b3, "NULL device pointer");
-  MRI_REQUIRE(d_w1 && d_b1 && d_w2 && d_b2 && d_w3 && d_b3 && loss_out, "NULL gradient pointer");
-  const int slab = slab_floats(hidden, k_in);
-  MRI_REQUIRE(workspace && workspace_bytes >= (int64_t)slab_count(hidden, k_in, n) * slab * 4,
-              "tiny MLP needs a workspace of %lld bytes (mri_tiny_mlp_workspace_bytes)",
-              (long long)slab_count(hidden, k_in, n) * slab * 4);
   FusedArgs a{};
   a.x = x, a.target = target;
   a.w1 = w1, a.b1 = b1, a.w2 = w2, a.b2 = b2, a.w3 = w3, a.b3 = b3;
-  a.y = y, a.dx = d_x, a.partial = static_cast<float*>(workspace);
+  a.y = y, a.dx = d_x;
   a.n = n, a.ld = ld, a.k_in = k_in;
-  a.grad_scale = (float)(2.0 / ((double)n_total * (double)grad_divisor));
-  a.inv_n = (float)(1.0 / (double)n_total);
   a.stagger = std::min(std::max(options().mlp_stagger, 0), 8);
   a.ready = overlap.ready, a.ready_target = overlap.target, a.status = overlap.status;
   a.dx_absmax = reinterpret_cast<unsigned int*>(dx_absmax);
+  const MlpGrads g{d_w1, d_b1, d_w2, d_b2, d_w3, d_b3, loss_out};
+  if (int rc = prepare_training(a, hidden, n_total, grad_divisor, g, workspace, workspace_bytes)) return rc;
   if (dx_absmax && !(use_x3(a, hidden) && d_x))
     return fail(MRI_ERR_UNSUPPORTED, "max |d_x| per feature pair comes from the bf16-pipe decoder kernel only "
                                      "(mri_tiny_mlp_dx_absmax_supported), with d_x requested");
   const int blocks = use_x3(a, hidden) ? x3_blocks(n) : pick_blocks(hidden, n);
-  const int slabs = blocks;
   if (int rc = dispatch(a, hidden, true, blocks, (hipStream_t)stream)) return rc;
-  ReduceArgs r{};
-  r.partial = a.partial, r.slabs = slabs, r.slab = slab, r.n_seg = 7, r.overwrite = overwrite;
-  const int lens[7] = {hidden * k_in, hidden, hidden * hidden, hidden, hidden, 1, 1};
-  float* dsts[7] = {d_w1, d_b1, d_w2, d_b2, d_w3, d_b3, loss_out};
-  int off = 0;
-  for (int g = 0; g < 7; ++g) {
-    r.seg_begin[g] = off, r.seg_len[g] = lens[g], r.dst[g] = dsts[g];
-    off += lens[g];
-  }
-  hipLaunchKernelGGL(slab_reduce_kernel, dim3((unsigned)ceil_div(slab, 64)), dim3(256), 0,
-                     (hipStream_t)stream, r);
-  return check_launch("slab_reduce_kernel");
+  return reduce_training(a, hidden, blocks, overwrite, g, (hipStream_t)stream);
 }
 
 extern "C" int mri_tiny_mlp_train(const float* x, const float* target, int64_t n, int32_t k_in,
@@ -1121,39 +1089,23 @@ extern "C" int mri_hash_tiny_mlp_train(const mri_grid_desc* grid, const float* t
   const int k_in = 2 * grid->n_levels;
   MRI_REQUIRE(table && coords && target && w1 && b1 && w2 && b2 && w3 && b3, "NULL device pointer");
   MRI_REQUIRE(table_aligned(grid, table), kTableAlignment);
-  MRI_REQUIRE(d_w1 && d_b1 && d_w2 && d_b2 && d_w3 && d_b3 && loss_out, "NULL gradient pointer");
+  const MlpGrads g{d_w1, d_b1, d_w2, d_b2, d_w3, d_b3, loss_out};
+  // (prepare_training checks these again; here so that a NULL gradient is still reported ahead of a bad d_enc_ld)
+  MRI_REQUIRE(g.w1 && g.b1 && g.w2 && g.b2 && g.w3 && g.b3 && g.loss, "NULL gradient pointer");
   MRI_REQUIRE(!d_enc || d_enc_ld >= n, "d_enc rows are %lld apart, batch of %lld", (long long)d_enc_ld,
               (long long)n);
-  const int slab = slab_floats(hidden, k_in);
-  const int blocks = x3_blocks(n);
-  // (what mri_tiny_mlp_workspace_bytes reports, as for the other training calls: the 64-wide f32-MFMA kernel's
-  // slab count may exceed this kernel's, and one byte less than reported is refused by every call alike)
-  MRI_REQUIRE(workspace && workspace_bytes >= (int64_t)slab_count(hidden, k_in, n) * slab * 4,
-              "needs a workspace of %lld bytes (mri_tiny_mlp_workspace_bytes)",
-              (long long)slab_count(hidden, k_in, n) * slab * 4);
   FusedArgs a{};
   a.target = target;
   a.w1 = w1, a.b1 = b1, a.w2 = w2, a.b2 = b2, a.w3 = w3, a.b3 = b3;
-  a.y = y, a.dx = d_enc, a.partial = static_cast<float*>(workspace);
+  a.y = y, a.dx = d_enc;
   a.n = n, a.ld = d_enc ? d_enc_ld : n, a.k_in = k_in;
-  MRI_REQUIRE(x3_addressable(a), "d_enc block beyond 32-bit lane offsets");
-  a.grad_scale = (float)(2.0 / ((double)n * (double)grad_divisor));
-  a.inv_n = (float)(1.0 / (double)n);
   EncodeArgs e{};
   e.coords = coords, e.table = table, e.tab = make_tab(grid), e.n_levels = grid->n_levels, e.dim = grid->dim;
+  if (int rc = prepare_training(a, hidden, n, grad_divisor, g, workspace, workspace_bytes)) return rc;
+  MRI_REQUIRE(x3_addressable(a), "d_enc block beyond 32-bit lane offsets");
+  const int blocks = x3_blocks(n);
   if (int rc = launch_tiny_mlp_x3_encoded(a, e, hidden, blocks, (hipStream_t)stream)) return rc;
-  ReduceArgs r{};
-  r.partial = a.partial, r.slabs = blocks, r.slab = slab, r.n_seg = 7, r.overwrite = overwrite ? 1 : 0;
-  const int lens[7] = {hidden * k_in, hidden, hidden * hidden, hidden, hidden, 1, 1};
-  float* dsts[7] = {d_w1, d_b1, d_w2, d_b2, d_w3, d_b3, loss_out};
-  int off = 0;
-  for (int g = 0; g < 7; ++g) {
-    r.seg_begin[g] = off, r.seg_len[g] = lens[g], r.dst[g] = dsts[g];
-    off += lens[g];
-  }
-  hipLaunchKernelGGL(slab_reduce_kernel, dim3((unsigned)ceil_div(slab, 64)), dim3(256), 0,
-                     (hipStream_t)stream, r);
-  return check_launch("slab_reduce_kernel");
+  return reduce_training(a, hidden, blocks, overwrite ? 1 : 0, g, (hipStream_t)stream);
 }
 
 extern "C" int mri_tiny_mlp_dx_absmax_supported(int32_t k_in, int32_t hidden) {

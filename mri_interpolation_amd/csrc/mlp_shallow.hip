@@ -21,10 +21,11 @@
 //       LDS image [h or k][row] and read back with the row on the k axis.
 //   dw2, db1: per-lane sums over the rounds, reduced over the 16 row lanes once at the end; db2 and
 //       the loss likewise.  The four waves add their parts in wave order in LDS, the workgroup writes ONE
-//       slab of partial sums to the workspace, and shallow_reduce_kernel adds the slabs in a fixed order:
+//       slab of partial sums to the workspace, and slab_reduce_kernel<16, 5> (slab.h) adds the slabs in a fixed order:
 //       no float atomics, bitwise reproducible.  The grid depends on n alone.
 #include "common.h"
 #include "device_math.h"
+#include "slab.h"
 
 #include <algorithm>
 
@@ -257,8 +258,9 @@ __global__ __launch_bounds__(kThreads) void shallow_mlp_kernel(const ShallowArgs
   }
   if (!TRAIN) return;
 
-  // one slab per workgroup: [dW1 (H, k_in)] [db1 H] [dw2 H] [db2] [loss], the waves added in wave order
-  const int slab = H * k_in + 2 * H + 2;
+  // one slab per workgroup (ShallowSlab), the waves added in wave order
+  const ShallowSlab lay{H, k_in};
+  const int slab = lay.floats();
 #pragma unroll
   for (int t = 0; t < T; ++t)
 #pragma unroll
@@ -277,68 +279,26 @@ __global__ __launch_bounds__(kThreads) void shallow_mlp_kernel(const ShallowArgs
 #pragma unroll
         for (int kt = 0; kt < KT; ++kt) {
           const int kk = 16 * kt + j;
-          if (kk < k_in) red[h * k_in + kk] = w ? red[h * k_in + kk] + dw1[t][kt][q] : dw1[t][kt][q];
+          float* p_w1 = lay.w1(red);
+          if (kk < k_in) p_w1[h * k_in + kk] = w ? p_w1[h * k_in + kk] + dw1[t][kt][q] : dw1[t][kt][q];
         }
         if (j == 0) {
-          float* p = red + H * k_in + h;
-          p[0] = w ? p[0] + db1[t][q] : db1[t][q];
-          p[H] = w ? p[H] + dw2[t][q] : dw2[t][q];
+          float* pb = lay.b1(red) + h;
+          float* pw = lay.w2(red) + h;
+          *pb = w ? *pb + db1[t][q] : db1[t][q];
+          *pw = w ? *pw + dw2[t][q] : dw2[t][q];
         }
       }
     if (lane == 0) {
-      float* p = red + H * k_in + 2 * H;
-      p[0] = w ? p[0] + db2 : db2;
-      p[1] = w ? p[1] + loss : loss;
+      float* pb = lay.b2(red);
+      float* pl = lay.loss(red);
+      *pb = w ? *pb + db2 : db2;
+      *pl = w ? *pl + loss : loss;
     }
   }
   __syncthreads();
   float* out = a.partial + (int64_t)blockIdx.x * slab;
-  for (int e = threadIdx.x; e < slab; e += kThreads) out[e] = e == slab - 1 ? red[e] * a.inv_n : red[e];
-}
-
-// Sum the per-workgroup slabs in a fixed order into the gradient tensors.
-struct ShallowReduceArgs {
-  const float* partial;
-  int slabs, slab, overwrite;
-  int seg_begin[5];
-  float* dst[5];
-};
-
-constexpr int kReduceGroups = 16;
-
-__global__ __launch_bounds__(64 * kReduceGroups) void shallow_reduce_kernel(const ShallowReduceArgs r) {
-  // 64 elements per workgroup; 16 thread groups each sum a sixteenth of the slabs in slab order (8 loads in
-  // flight: the kernel is bound by the latency of its dependent rounds of loads, not by bytes), then the
-  // sixteen parts are added in a fixed order -> same bits every run.
-  __shared__ float part[kReduceGroups][64];
-  const int e = blockIdx.x * 64 + (threadIdx.x & 63), grp = threadIdx.x >> 6;
-  const int per = (r.slabs + kReduceGroups - 1) / kReduceGroups;
-  const int b_lo = grp * per, b_hi = min(r.slabs, b_lo + per);
-  float s = 0.f;
-  if (e < r.slab) {
-    const float* p = r.partial + e;
-    int b = b_lo;
-    for (; b + 8 <= b_hi; b += 8) {
-      float v[8];
-#pragma unroll
-      for (int i = 0; i < 8; ++i) v[i] = p[(int64_t)(b + i) * r.slab];
-#pragma unroll
-      for (int i = 0; i < 8; ++i) s += v[i];
-    }
-    for (; b < b_hi; ++b) s += p[(int64_t)b * r.slab];
-  }
-  part[grp][threadIdx.x & 63] = s;
-  __syncthreads();
-  if (grp != 0 || e >= r.slab) return;
-  s = part[0][threadIdx.x];
-#pragma unroll
-  for (int i = 1; i < kReduceGroups; ++i) s += part[i][threadIdx.x];
-  int seg = 0;
-#pragma unroll
-  for (int i = 1; i < 5; ++i)
-    if (e >= r.seg_begin[i]) seg = i;
-  float* dst = r.dst[seg] + (e - r.seg_begin[seg]);
-  *dst = r.overwrite ? s : *dst + s;
+  for (int e = threadIdx.x; e < slab; e += kThreads) out[e] = e == lay.loss(0) ? red[e] * a.inv_n : red[e];
 }
 
 bool act_ok(int act) { return act == MRI_ACT_IDENTITY || act == MRI_ACT_RELU || act == MRI_ACT_GELU; }
@@ -355,8 +315,6 @@ int block_rows(int hidden) { return kWaves * (hidden <= 32 ? 32 : 16); }
 int pick_blocks(int hidden, int64_t n) {
   return (int)std::min<int64_t>(ceil_div(n, block_rows(hidden)), kMaxBlocks);
 }
-
-int slab_floats(int hidden, int k_in) { return hidden * k_in + 2 * hidden + 2; }
 
 template <int H, int KP, int CT>
 void launch_one(const ShallowArgs& a, bool train, int blocks, hipStream_t st) {
@@ -390,7 +348,7 @@ extern "C" int mri_shallow_mlp_supported(int32_t k_in, int32_t hidden, int32_t d
 
 extern "C" int64_t mri_shallow_mlp_workspace_bytes(int32_t k_in, int32_t hidden, int64_t n) {
   if (!supported(k_in, hidden, 1, MRI_ACT_IDENTITY, MRI_ACT_IDENTITY)) return -1;
-  return (int64_t)pick_blocks(hidden, std::max<int64_t>(n, 1)) * slab_floats(hidden, k_in) * 4;
+  return (int64_t)pick_blocks(hidden, std::max<int64_t>(n, 1)) * ShallowSlab{hidden, k_in}.floats() * 4;
 }
 
 extern "C" int mri_shallow_mlp_forward(const float* x, int64_t n, int32_t k_in, int32_t hidden, const float* w1,
@@ -422,7 +380,8 @@ extern "C" int mri_shallow_mlp_train(const float* x, const float* target, int64_
   if (n == 0) return MRI_OK;
   MRI_REQUIRE(x && target && w1 && b1 && w2 && b2, "NULL device pointer");
   MRI_REQUIRE(d_w1 && d_b1 && d_w2 && d_b2 && loss_out, "NULL gradient pointer");
-  const int slab = slab_floats(hidden, k_in);
+  const ShallowSlab lay{hidden, k_in};
+  const int slab = lay.floats();
   const int blocks = pick_blocks(hidden, n);
   MRI_REQUIRE(workspace && workspace_bytes >= (int64_t)blocks * slab * 4,
               "shallow decoder needs a workspace of %lld bytes (mri_shallow_mlp_workspace_bytes)",
@@ -434,12 +393,6 @@ extern "C" int mri_shallow_mlp_train(const float* x, const float* target, int64_
   a.grad_scale = (float)(2.0 / ((double)n_total * (double)grad_divisor));
   a.inv_n = (float)(1.0 / (double)n_total);
   if (int rc = launch(a, hidden, true, (hipStream_t)stream)) return rc;
-  ShallowReduceArgs r{};
-  r.partial = a.partial, r.slabs = blocks, r.slab = slab, r.overwrite = overwrite ? 1 : 0;
-  const int lens[5] = {hidden * k_in, hidden, hidden, 1, 1};
-  float* dsts[5] = {d_w1, d_b1, d_w2, d_b2, loss_out};
-  for (int i = 0, off = 0; i < 5; off += lens[i], ++i) r.seg_begin[i] = off, r.dst[i] = dsts[i];
-  hipLaunchKernelGGL(shallow_reduce_kernel, dim3((unsigned)ceil_div(slab, 64)), dim3(64 * kReduceGroups), 0,
-                     (hipStream_t)stream, r);
-  return check_launch("shallow_reduce_kernel");
+  return reduce_slabs<16>(a.partial, blocks, slab, segments(lay, overwrite ? 1 : 0, d_w1, d_b1, d_w2, d_b2, loss_out),
+                          (hipStream_t)stream);
 }

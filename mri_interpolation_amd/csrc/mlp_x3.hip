@@ -819,13 +819,14 @@ __global__ __launch_bounds__(kX3Threads / U) void tiny_mlp_x3_kernel(const Fused
   }
 
   // ---- this workgroup's slab: every element of dW2 / dW1 has exactly one owner lane ----------------
-  float* slab = a.partial + (int64_t)blockIdx.x * slab_floats(H, a.k_in);
-  float* p_w1 = slab;
-  float* p_b1 = p_w1 + H * a.k_in;
-  float* p_w2 = p_b1 + H;
-  float* p_b2 = p_w2 + H * H;
-  float* p_w3 = p_b2 + H;
-  float* p_b3 = p_w3 + H;
+  const MlpSlab lay{H, a.k_in};
+  float* slab = a.partial + (int64_t)blockIdx.x * lay.floats();
+  float* p_w1 = lay.w1(slab);
+  float* p_b1 = lay.b1(slab);
+  float* p_w2 = lay.w2(slab);
+  float* p_b2 = lay.b2(slab);
+  float* p_w3 = lay.w3(slab);
+  float* p_b3 = lay.b3(slab);
 #pragma unroll
   for (int u = 0; u < U; ++u) {
     const int n = unit0(u) + 4 * g;
@@ -844,7 +845,7 @@ __global__ __launch_bounds__(kX3Threads / U) void tiny_mlp_x3_kernel(const Fused
   }
   if (w == 0 && lane == 0) {
     p_b3[0] = s_b3;
-    p_b3[1] = s_loss * a.inv_n;
+    *lay.loss(slab) = s_loss * a.inv_n;
   }
   X3P_MARK(21)
   X3P_END

@@ -261,15 +261,6 @@ __global__ __launch_bounds__(kThreads) void modsiren_forward_kernel(const ModArg
   }
 }
 
-// loss_out[0] += the workgroups' loss shares, in workgroup order
-__global__ __launch_bounds__(64) void modsiren_loss_reduce_kernel(const float* __restrict__ partial, int slabs,
-                                                                  float* __restrict__ loss_out) {
-  if (threadIdx.x != 0 || blockIdx.x != 0) return;
-  float sum = 0.f;
-  for (int b = 0; b < slabs; ++b) sum += partial[b];
-  loss_out[0] += sum;
-}
-
 // ------------------------------------------------------------------------------------------------------------------
 // Backward chain.  Per tile, from the head down, with da_l and g_l = dzm_{l+1} Wm_{l+1}[:, :H] in accumulator registers:
 //   dzs_l = da_l (.) [h_l w_l cos]          dzm_l = (da_l (.) s_l + g_l) (.) [h_l > 0]     (ReLU'(0) = 0, as torch)
@@ -290,12 +281,9 @@ struct ModBwdArgs {
   const float* sn[kMaxSine];
   float* dzs[kMaxSine];          // (n, H) for l >= 1 ([0] unused)
   float* dzm[kMaxSine];
-  float* partial;                // [gridDim.x][mod_slab_floats]
+  float* partial;                // [gridDim.x][ModBwdSlab]
   const char* wtsplit;           // per layer l = 1 .. L-1: split Ws_l^T | split Wm_l[:, :H]^T
 };
-
-// slab: dWm small-K [L][H][8] | dWs_0 [H][8] | dbm [L][H] | dbs [L][H] | dW_head [H] | db_head (padded to 4)
-__host__ __device__ inline int mod_slab_floats(int H, int L) { return (L + 1) * H * kMaxIn + 2 * L * H + H + 4; }
 
 template <class S>
 struct MBwdSmem {
@@ -331,13 +319,14 @@ __global__ __launch_bounds__(kThreads) void modsiren_backward_kernel(const ModBw
   const int lane_off = (rb * 32 + 4 * lh) * H + n0;
   const int64_t smb = split_matrix_bytes(H);
 
-  float* const slab = a.partial + (int64_t)blockIdx.x * mod_slab_floats(H, L);
-  float* const p_wm = slab;
-  float* const p_ws0 = p_wm + L * H * kMaxIn;
-  float* const p_bm = p_ws0 + H * kMaxIn;
-  float* const p_bs = p_bm + L * H;
-  float* const p_wh = p_bs + L * H;
-  float* const p_bh = p_wh + H;
+  const ModBwdSlab lay{H, L};
+  float* const slab = a.partial + (int64_t)blockIdx.x * lay.floats();
+  float* const p_wm = lay.wm(slab, 0);
+  float* const p_ws0 = lay.ws0(slab);
+  float* const p_bm = lay.bm(slab, 0);
+  float* const p_bs = lay.bs(slab, 0);
+  float* const p_wh = lay.w_head(slab);
+  float* const p_bh = lay.b_head(slab);
 
   ChunkStream<S, -1> stream(L - 1, tiles);
   auto issue2 = [&](int layer, int kc, int buf) {
@@ -511,55 +500,6 @@ __global__ __launch_bounds__(kThreads) void modsiren_backward_kernel(const ModBw
   }
 }
 
-// Sum the backward slabs in workgroup order and add them to the gradient tensors.
-struct ModReduceArgs {
-  const float* partial;
-  int slabs, hidden, L, dim_in;
-  float* d_ws[kMaxSine + 1];
-  float* d_bs[kMaxSine + 1];
-  float* d_wm[kMaxSine];
-  float* d_bm[kMaxSine];
-};
-
-__global__ __launch_bounds__(256) void modsiren_bwd_reduce_kernel(const ModReduceArgs r) {
-  const int H = r.hidden, L = r.L, D = r.dim_in;
-  const int slab = mod_slab_floats(H, L);
-  const int e = blockIdx.x * 256 + threadIdx.x;
-  if (e >= slab) return;
-  const int o_ws0 = L * H * kMaxIn, o_bm = o_ws0 + H * kMaxIn, o_bs = o_bm + L * H, o_wh = o_bs + L * H, o_bh = o_wh + H;
-  float* dst = nullptr;
-  if (e < o_ws0) {
-    const int l = e / (H * kMaxIn), col = (e / kMaxIn) % H, d = e % kMaxIn;
-    if (d < D) dst = l == 0 ? r.d_wm[0] + col * D + d : r.d_wm[l] + col * (H + D) + H + d;
-  } else if (e < o_bm) {
-    const int q = e - o_ws0, col = q / kMaxIn, d = q % kMaxIn;
-    if (d < D) dst = r.d_ws[0] + col * D + d;
-  } else if (e < o_bs) {
-    const int q = e - o_bm;
-    dst = r.d_bm[q / H] + q % H;
-  } else if (e < o_wh) {
-    const int q = e - o_bs;
-    dst = r.d_bs[q / H] + q % H;
-  } else if (e < o_bh) {
-    dst = r.d_ws[L] + (e - o_wh);
-  } else if (e == o_bh) {
-    dst = r.d_bs[L];
-  }
-  if (!dst) return;  // (padding, and the d >= dim_in entries no workgroup writes)
-  float sum = 0.f;
-  const float* p = r.partial + e;
-  int b = 0;
-  for (; b + 8 <= r.slabs; b += 8) {
-    float v[8];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) v[j] = p[(int64_t)(b + j) * slab];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) sum += v[j];
-  }
-  for (; b < r.slabs; ++b) sum += p[(int64_t)b * slab];
-  *dst += sum;
-}
-
 // ------------------------------------------------------------------------------------------------------ host side
 bool mod_supported(int dim_in, int hidden, int n_layers, int dim_out) {
   return (hidden == 64 || hidden == 128) && dim_in >= 1 && dim_in <= kMaxIn && n_layers >= 2 &&
@@ -573,7 +513,7 @@ int mod_tile_rows(int hidden) { return hidden == 128 ? 64 : 128; }
 int mod_blocks(int hidden, int64_t n) { return (int)std::min<int64_t>(ceil_div(n, mod_tile_rows(hidden)), 256); }
 int64_t mod_split_bytes(int hidden, int L) { return 2 * (int64_t)(L - 1) * split_matrix_bytes(hidden); }
 int64_t mod_slab_bytes(int64_t n, int hidden, int L) {
-  const int64_t chain = std::max<int64_t>((int64_t)mod_blocks(hidden, n) * mod_slab_floats(hidden, L), 256);
+  const int64_t chain = std::max<int64_t>((int64_t)mod_blocks(hidden, n) * ModBwdSlab{hidden, L}.floats(), 256);
   const int64_t bytes = std::max(chain, wgrad_slab_floats(n, hidden)) * 4;
   return (bytes + 255) / 256 * 256;
 }
@@ -692,8 +632,9 @@ extern "C" int mri_modsiren_forward_loss(const float* x, const float* target, in
   hipStream_t st = (hipStream_t)stream;
   if (int rc = mod_split(siren_weight, mod_weight, dim_in, hidden, n_layers, false, wsplit, st)) return rc;
   if (int rc = launch_mod_forward(hidden, a, 2, st)) return rc;
-  hipLaunchKernelGGL(modsiren_loss_reduce_kernel, dim3(1), dim3(64), 0, st, a.partial, mod_blocks(hidden, n), loss_out);
-  return check_launch("modsiren_loss_reduce_kernel");
+  SegmentTable<1> t{};  // slabs of one float: the workgroups' loss shares, added in workgroup order
+  t.vector(0, 1, loss_out);
+  return reduce_slabs<1>(a.partial, mod_blocks(hidden, n), 1, t, st);
 }
 
 extern "C" int mri_modsiren_backward(const float* x, const float* dy, int64_t n, int32_t dim_in, int32_t hidden,
@@ -716,12 +657,9 @@ extern "C" int mri_modsiren_backward(const float* x, const float* dy, int64_t n,
               "(mri_modsiren_backward_workspace_bytes)", (long long)need);
   ModBwdArgs a{};
   a.x = x, a.dy = dy, a.n = n, a.dim_in = dim_in, a.L = L;
-  ModReduceArgs r{};
-  for (int l = 0; l <= L; ++l) {
+  for (int l = 0; l <= L; ++l)
     MRI_REQUIRE(siren_weight[l] && d_siren_weight[l] && d_siren_bias[l],
                 "NULL SIREN parameter / gradient pointer (layer %d)", l);
-    r.d_ws[l] = d_siren_weight[l], r.d_bs[l] = d_siren_bias[l];
-  }
   for (int l = 0; l < L; ++l) {
     MRI_REQUIRE(mod_weight[l] && d_mod_weight[l] && d_mod_bias[l],
                 "NULL modulator parameter / gradient pointer (layer %d)", l);
@@ -731,7 +669,6 @@ extern "C" int mri_modsiren_backward(const float* x, const float* dy, int64_t n,
                 "act / hid / dcos / sn buffers must be 16-byte aligned (layer %d)", l);
     MRI_REQUIRE(l == 0 || (aligned_to(dzs[l], 16) && aligned_to(dzm[l], 16)), "dzs / dzm buffers must be 16-byte aligned (layer %d)",
                 l);
-    r.d_wm[l] = d_mod_weight[l], r.d_bm[l] = d_mod_bias[l];
     a.hid[l] = hid[l], a.dcos[l] = dcos[l], a.sn[l] = sn[l], a.dzs[l] = dzs[l], a.dzm[l] = dzm[l];
   }
   a.w_head = siren_weight[L], a.act_last = act[L - 1];
@@ -746,10 +683,10 @@ extern "C" int mri_modsiren_backward(const float* x, const float* dy, int64_t n,
         return check_launch("modsiren_backward_kernel");
       }))
     return rc;
-  r.partial = a.partial, r.slabs = blocks, r.hidden = hidden, r.L = L, r.dim_in = dim_in;
-  hipLaunchKernelGGL(modsiren_bwd_reduce_kernel, dim3((unsigned)ceil_div(mod_slab_floats(hidden, L), 256)), dim3(256),
-                     0, st, r);
-  if (int rc = check_launch("modsiren_bwd_reduce_kernel")) return rc;
+  const ModBwdSlab lay{hidden, L};
+  if (int rc = reduce_slabs<1>(a.partial, blocks, lay.floats(),
+                               segments(lay, dim_in, d_siren_weight, d_siren_bias, d_mod_weight, d_mod_bias), st))
+    return rc;
   for (int l = L - 1; l >= 1; --l) {  // dWs_l = dzs_l^T a_{l-1};  dWm_l[:, :H] = dzm_l^T h_{l-1}
     WgradArgs g{};
     g.n = n, g.partial = static_cast<float*>(workspace);

@@ -11,11 +11,9 @@
 #include "bf16x3.h"
 #include "chain_tile.h"
 #include "common.h"
+#include "slab.h"
 
 namespace mri {
-
-constexpr int kMaxSine = MRI_SIREN_MAX_LAYERS;  // sine layers, the first one included
-constexpr int kMaxIn = 8;
 
 struct ChainArgs {
   const float* x;                   // (n, dim_in) row-major
@@ -32,13 +30,10 @@ struct ChainArgs {
   const float* target;              // (n)
   float grad_scale, inv_n;          // 2 / (n_total divisor), 1 / n_total
   float* dz_last;                   // (n, H): dLoss / d(pre-activation of the last sine layer)
-  float* partial;                   // [gridDim.x][fwd_slab_floats]
+  float* partial;                   // [gridDim.x][SirenFwdSlab]
   const char* wsplit;               // split W of layers 1 .. n_sine-1 (split_matrix_bytes each)
   float* dy_ws;                     // siren_rows.hip, loss mode: dLoss/dy per row, in the workspace (rows_dy_offset)
 };
-
-// loss-mode slab: dW_head [H] | db_last [H] | db_head, loss (padded to 4)
-__host__ __device__ inline int fwd_slab_floats(int hidden) { return 2 * hidden + 4; }
 
 // Split weights (siren_split_weights_kernel): per H x H matrix, chunk kc = contraction indices
 // [16 kc, 16 kc + 16), term planes h | m | l of [H rows][2 slots][8 bf16]; slot q of row n holds
@@ -56,16 +51,11 @@ struct BwdArgs {
   const float* act_last;           // (n, H): output of the last sine layer
   const float* deriv[kMaxSine];    // (n, H) per sine layer: w0 cos(.)
   float* dz[kMaxSine];             // (n, H) for sine layers 1 .. n_sine-1 ([0] unused)
-  float* partial;                  // [gridDim.x][bwd_slab_floats]
+  float* partial;                  // [gridDim.x][SirenBwdSlab]
   const char* wtsplit;             // split W^T of layers 1 .. n_sine-1 (split_matrix_bytes each)
   int head_done;                   // dz[n_sine-1] is an INPUT (the forward kernel's loss mode wrote it)
   const float* dy_ws;              // siren_rows.hip: dLoss/dy per row, where the loss-mode forward kernel left it
 };
-
-// slab: dW_head [H] | db_head [1] (padded to 4) | db_l [n_sine][H] | dW_first [H][kMaxIn]
-__host__ __device__ inline int bwd_slab_floats(int hidden, int n_sine) {
-  return hidden + 4 + n_sine * hidden + hidden * kMaxIn;
-}
 
 
 struct WgradArgs {

@@ -290,7 +290,8 @@ __global__ __launch_bounds__(kThreads) void siren_forward_kernel(const ChainArgs
   SP_END
   if (LOSS) {
     // ---- this workgroup's slab: dW_head, db of the last sine layer, db_head, loss -----------------
-    float* slab = a.partial + (int64_t)blockIdx.x * fwd_slab_floats(H);
+    const SirenFwdSlab lay{H};
+    float* slab = a.partial + (int64_t)blockIdx.x * lay.floats();
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     __syncthreads();
     float* red = sm.img;  // scratch: [row block][H] per quantity
@@ -308,8 +309,8 @@ __global__ __launch_bounds__(kThreads) void siren_forward_kernel(const ChainArgs
       float wh = 0.f, bl = 0.f;
 #pragma unroll
       for (int q = 0; q < S::RB; ++q) wh += red[q * H + tid], bl += red[(S::RB + q) * H + tid];
-      slab[tid] = wh;
-      slab[H + tid] = bl;
+      lay.w_head(slab)[tid] = wh;
+      lay.b_last(slab)[tid] = bl;
     }
     __syncthreads();
     red[tid] = ln.lane == 0 ? g_bhead : 0.f;  // lane 0 of each wave holds its rows' sums
@@ -318,7 +319,8 @@ __global__ __launch_bounds__(kThreads) void siren_forward_kernel(const ChainArgs
     if (tid == 0) {
       float sb = 0.f, sl = 0.f;
       for (int w = 0; w < 8; ++w) sb += red[w * 64], sl += red[kThreads + w * 64];
-      slab[2 * H] = sb, slab[2 * H + 1] = sl * a.inv_n, slab[2 * H + 2] = 0.f, slab[2 * H + 3] = 0.f;
+      float* p = lay.b_head(slab);  // the four-float field: db_head, loss (SirenFwdSlab::loss), two floats of padding
+      p[0] = sb, p[1] = sl * a.inv_n, p[2] = 0.f, p[3] = 0.f;
     }
   }
 }
@@ -335,7 +337,7 @@ __global__ __launch_bounds__(kThreads) void siren_forward_kernel(const ChainArgs
 //   first    dW_first = dz_0^T x on the VALU (K = dim_in)
 // dz_l (l >= 1) leaves for HBM once: siren_wgrad_kernel contracts it with a_{l-1} over the batch.
 // Partial sums (biases, head, first layer) leave through one slab per workgroup, summed in a
-// fixed order by siren_bwd_reduce_kernel (bitwise reproducible, no float atomics).
+// fixed order by slab_reduce_kernel<1, N> (slab.h: bitwise reproducible, no float atomics).
 template <class S>
 struct BwdSmem {
   char wbuf[2][S::chunk_bytes] __attribute__((aligned(16)));  // chunks of the split W^T: term planes [k][2 slots]
@@ -510,11 +512,12 @@ __global__ __launch_bounds__(kThreads) void siren_backward_kernel(const BwdArgs 
   }
 
   // ---- this workgroup's slab -------------------------------------------------------------------
-  float* slab = a.partial + (int64_t)blockIdx.x * bwd_slab_floats(H, L);
-  float* p_whead = slab;
-  float* p_bhead = slab + H;
-  float* p_b = slab + H + 4;
-  float* p_wfirst = p_b + L * H;
+  const SirenBwdSlab lay{H, L};
+  float* slab = a.partial + (int64_t)blockIdx.x * lay.floats();
+  float* p_whead = lay.w_head(slab);
+  float* p_bhead = lay.b_head(slab);
+  float* p_b = lay.b(slab, 0);
+  float* p_wfirst = lay.w_first(slab);
   __syncthreads();
   float* red = sm.img;  // scratch; (col, group) sums: `groups` partial sums per column
   auto column_sum = [&](const float* v) {
@@ -550,43 +553,6 @@ __global__ __launch_bounds__(kThreads) void siren_backward_kernel(const BwdArgs 
     float sb = 0.f;
     for (int c = 0; c < S::rows; ++c) sb += red[c];
     p_bhead[0] = sb, p_bhead[1] = 0.f, p_bhead[2] = 0.f, p_bhead[3] = 0.f;
-  }
-}
-
-// Sum the backward slabs in a fixed order and add them to the gradient tensors.
-struct BwdReduceArgs {
-  const float* partial;
-  int slabs, hidden, n_sine, dim_in;
-  float* d_w[kMaxSine + 1];
-  float* d_b[kMaxSine + 1];
-};
-
-__global__ __launch_bounds__(256) void siren_bwd_reduce_kernel(const BwdReduceArgs r) {
-  const int H = r.hidden, L = r.n_sine;
-  const int slab = bwd_slab_floats(H, L);
-  const int e = blockIdx.x * 256 + threadIdx.x;
-  if (e >= slab) return;
-  float sum = 0.f;
-  const float* p = r.partial + e;
-  int b = 0;
-  for (; b + 8 <= r.slabs; b += 8) {
-    float v[8];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) v[j] = p[(int64_t)(b + j) * slab];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) sum += v[j];
-  }
-  for (; b < r.slabs; ++b) sum += p[(int64_t)b * slab];
-  if (e < H) {
-    r.d_w[L][e] += sum;                                      // head weight (1, H)
-  } else if (e < H + 4) {
-    if (e == H) r.d_b[L][0] += sum;                          // head bias
-  } else if (e < H + 4 + L * H) {
-    const int q = e - H - 4;
-    r.d_b[q / H][q % H] += sum;                              // sine-layer biases
-  } else {
-    const int q = e - H - 4 - L * H, o = q / kMaxIn, d = q % kMaxIn;
-    if (d < r.dim_in) r.d_w[0][o * r.dim_in + d] += sum;     // first layer (H, dim_in)
   }
 }
 
@@ -782,38 +748,13 @@ __global__ __launch_bounds__(kThreads) void siren_wgrad_kernel(const WgradArgs g
         slab[(n_base + ti * 32 + acc_row(r, lh)) * H + k_base + tj * 32 + l31] = acc[ti][tj][r];
 }
 
-// dst[e] += sum over slabs of partial[slab][e], fixed order; the slab is a row-major matrix of `cols` columns and
-// dst one of row stride `ld` (ld > cols: the H x H block in front of a modulator layer's (H, H + dim_in) weight).
-// There are 256 x wgrad_split slabs (2048 at H = 32, 512 at H = 64) of signed terms, and one float32 chain that long
-// moved an H x H gradient by up to 3.7e-6 of its largest element when the same rows were cut into two launches
-// (tests/test_gpu_tile_loop.py).  So eight slabs meet in a float32 tree (three roundings deep) and the trees' sums
-// are added in float64.  A thread waits for a round of loads before it issues the next, and what it computes behind
-// the last load of a round is exposed: sixteen loads a round, so that the longer tail comes half as often.
-__device__ __forceinline__ float sum8(const float* v) {
-  return ((v[0] + v[1]) + (v[2] + v[3])) + ((v[4] + v[5]) + (v[6] + v[7]));
-}
-
-__global__ __launch_bounds__(256) void slab_sum_kernel(const float* __restrict__ partial, int slabs,
-                                                       int count, float* __restrict__ dst, int cols, int ld) {
+// The H x H slabs of siren_wgrad_kernel, added in the tree order of slab.h into `to`: a row-major matrix whose rows may be
+// further apart than H (the H x H block in front of a modulator layer's (H, H + dim_in) weight).
+__global__ __launch_bounds__(256) void slab_sum_kernel(const float* __restrict__ partial, int slabs, int count,
+                                                       const SlabDest to) {
   const int e = blockIdx.x * 256 + threadIdx.x;
   if (e >= count) return;
-  const float* p = partial + e;
-  double sum = 0.0;
-  int b = 0;
-  for (; b + 16 <= slabs; b += 16) {
-    float v[16];
-#pragma unroll
-    for (int j = 0; j < 16; ++j) v[j] = p[(int64_t)(b + j) * count];
-    sum += (double)sum8(v) + (double)sum8(v + 8);
-  }
-  for (; b + 8 <= slabs; b += 8) {
-    float v[8];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) v[j] = p[(int64_t)(b + j) * count];
-    sum += (double)sum8(v);
-  }
-  for (; b < slabs; ++b) sum += (double)p[(int64_t)b * count];
-  dst[ld == cols ? e : (e / cols) * ld + e % cols] += (float)sum;
+  to.write(e, tree_column_sum(partial + e, slabs, count), 0);
 }
 
 // Three-term split of the H x H weights into the chunk-major planes issue_chunk streams (layout:
@@ -903,7 +844,7 @@ int launch_wgrad(const WgradArgs& g, float* d_weight, hipStream_t st, int ld) {
   const int wb = wgrad_blocks(g.n);
   hipLaunchKernelGGL((siren_wgrad_kernel<W>), dim3(wb), dim3(kThreads), 0, st, g);
   hipLaunchKernelGGL(slab_sum_kernel, dim3((unsigned)ceil_div(H * H, 256)), dim3(256), 0, st,
-                     g.partial, wb * W::RS, H * H, d_weight, H, ld);
+                     g.partial, wb * W::RS, H * H, SlabDest{d_weight, H, H, ld});
   return check_launch("siren_wgrad_kernel");
 }
 
@@ -913,42 +854,6 @@ int forward_any(int hidden, const ChainArgs& a, int mode, hipStream_t st) {
       (mode != 2 || rows_backward_supported(hidden, a.n_sine, a.dim_in, 1)))
     return forward_rows(a, mode, st);
   return dispatch_hidden(hidden, [&](auto h) { return launch_forward<decltype(h)::value>(a, mode, st); });
-}
-
-// loss-mode slabs -> head weight / bias gradient, last sine layer's bias gradient, loss
-struct FwdReduceArgs {
-  const float* partial;
-  int slabs, hidden;
-  float* d_w_head;
-  float* d_b_head;
-  float* d_b_last;
-  float* loss_out;
-};
-
-__global__ __launch_bounds__(256) void siren_fwd_reduce_kernel(const FwdReduceArgs r) {
-  const int H = r.hidden, slab = fwd_slab_floats(H);
-  const int e = blockIdx.x * 256 + threadIdx.x;
-  if (e >= slab) return;
-  // (eight loads in flight, the additions in slab order: a load per addition was 63 us of dependent round trips)
-  float sum = 0.f;
-  const float* p = r.partial + e;
-  int b = 0;
-  for (; b + 8 <= r.slabs; b += 8) {
-    float v[8];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) v[j] = p[(int64_t)(b + j) * slab];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) sum += v[j];
-  }
-  for (; b < r.slabs; ++b) sum += p[(int64_t)b * slab];
-  if (e < H)
-    r.d_w_head[e] += sum;
-  else if (e < 2 * H)
-    r.d_b_last[e - H] += sum;
-  else if (e == 2 * H)
-    r.d_b_head[0] += sum;
-  else if (e == 2 * H + 1)
-    r.loss_out[0] += sum;
 }
 
 int backward_any(int hidden, const BwdArgs& a, hipStream_t st) {
@@ -1114,19 +1019,15 @@ extern "C" int mri_siren_forward_loss(const float* x, const float* target, int64
                               options().siren_rows && rows_backward_supported(hidden, n_sine_layers, dim_in, 1) ? 1 : 0});
   if (int rc = split_weights(weight, n_sine_layers, hidden, false, wsplit, st)) return rc;
   if (int rc = forward_any(hidden, a, 2, st)) return rc;
-  FwdReduceArgs r{};
-  r.partial = a.partial, r.hidden = hidden;
-  r.slabs = options().siren_rows && rows_backward_supported(hidden, n_sine_layers, dim_in, 1) ? rows_blocks(n) : blocks;
-  r.d_w_head = d_w_head, r.d_b_head = d_b_head, r.d_b_last = d_b_last, r.loss_out = loss_out;
-  hipLaunchKernelGGL(siren_fwd_reduce_kernel, dim3((unsigned)ceil_div(fwd_slab_floats(hidden), 256)),
-                     dim3(256), 0, st, r);
-  return check_launch("siren_fwd_reduce_kernel");
+  const int slabs = options().siren_rows && rows_backward_supported(hidden, n_sine_layers, dim_in, 1) ? rows_blocks(n) : blocks;
+  const SirenFwdSlab lay{hidden};
+  return reduce_slabs<1>(a.partial, slabs, lay.floats(), segments(lay, d_w_head, d_b_last, d_b_head, loss_out), st);
 }
 
 namespace mri {
 namespace {
 int64_t slab_region_bytes(int64_t n, int hidden, int n_sine) {
-  const int64_t chain = (int64_t)chain_blocks(hidden, n) * bwd_slab_floats(hidden, n_sine);
+  const int64_t chain = (int64_t)chain_blocks(hidden, n) * SirenBwdSlab{hidden, n_sine}.floats();
   const int64_t wgrad = n_sine > 1 ? (int64_t)wgrad_blocks(n) * wgrad_split(hidden) * hidden * hidden : 0;
   int64_t bytes = std::max(chain, wgrad) * 4;
   // siren_rows.hip: dLoss/dy per row travels from the loss-mode forward to the backward kernel behind the slabs
@@ -1198,13 +1099,10 @@ extern "C" int mri_siren_backward(const float* x, const float* dy, int64_t n, in
                 rows ? 1 : 0, c.rows);
   }
   if (int rc = rows ? backward_rows(a, st) : backward_any(hidden, a, st)) return rc;
-  BwdReduceArgs r{};
-  r.partial = a.partial, r.slabs = rows ? rows_blocks(n) : chain_blocks(hidden, n), r.hidden = hidden, r.n_sine = L;
-  r.dim_in = dim_in;
-  for (int l = 0; l <= L; ++l) r.d_w[l] = d_weight[l], r.d_b[l] = d_bias[l];
-  hipLaunchKernelGGL(siren_bwd_reduce_kernel,
-                     dim3((unsigned)ceil_div(bwd_slab_floats(hidden, L), 256)), dim3(256), 0, st, r);
-  if (int rc = check_launch("siren_bwd_reduce_kernel")) return rc;
+  const SirenBwdSlab lay{hidden, L};
+  if (int rc = reduce_slabs<1>(a.partial, rows ? rows_blocks(n) : chain_blocks(hidden, n), lay.floats(),
+                               segments(lay, dim_in, d_weight, d_bias), st))
+    return rc;
   for (int l = L - 1; l >= 1; --l) {  // dW_l = dz_l^T a_{l-1}
     WgradArgs g{};
     g.dz = dz[l], g.act = act[l - 1], g.n = n, g.partial = static_cast<float*>(workspace);

@@ -662,16 +662,18 @@ __global__ __launch_bounds__(kThreadsR) void siren_forward_rows_kernel(const Cha
     for (int off = 16; off > 0; off >>= 1) sb += __shfl_xor(sb, off, 64), sl += __shfl_xor(sl, off, 64);
     if (lane == 0) red[8 * kH + wave] = sb, red[8 * kH + 4 + wave] = sl;
     __syncthreads();
-    float* slab = a.partial + (int64_t)blockIdx.x * fwd_slab_floats(kH);
+    const SirenFwdSlab lay{kH};
+    float* slab = a.partial + (int64_t)blockIdx.x * lay.floats();
     {
       const int f = tid;  // 256 threads = H
-      slab[f] = ((red[0 * kH + f] + red[2 * kH + f]) + red[4 * kH + f]) + red[6 * kH + f];
-      slab[kH + f] = 0.f;
+      lay.w_head(slab)[f] = ((red[0 * kH + f] + red[2 * kH + f]) + red[4 * kH + f]) + red[6 * kH + f];
+      lay.b_last(slab)[f] = 0.f;  // (the backward kernel's)
     }
     if (tid == 0) {
-      slab[2 * kH] = ((red[8 * kH] + red[8 * kH + 1]) + red[8 * kH + 2]) + red[8 * kH + 3];
-      slab[2 * kH + 1] = (((red[8 * kH + 4] + red[8 * kH + 5]) + red[8 * kH + 6]) + red[8 * kH + 7]) * a.inv_n;
-      slab[2 * kH + 2] = 0.f, slab[2 * kH + 3] = 0.f;
+      float* p = lay.b_head(slab);  // the four-float field: db_head, loss (SirenFwdSlab::loss), two floats of padding
+      p[0] = ((red[8 * kH] + red[8 * kH + 1]) + red[8 * kH + 2]) + red[8 * kH + 3];
+      p[1] = (((red[8 * kH + 4] + red[8 * kH + 5]) + red[8 * kH + 6]) + red[8 * kH + 7]) * a.inv_n;
+      p[2] = 0.f, p[3] = 0.f;
     }
   }
 }
@@ -843,7 +845,7 @@ __global__ __launch_bounds__(kThreadsR) void siren_backward_rows_kernel(const Bw
       // dz_{l-1} leaves for l - 1 >= 1; for l - 1 = 0 the same stores go to a dummy (the head of this workgroup's slab,
       // written again at the kernel's end): no branch in the tile loop
       const bool keep = l - 1 >= 1;
-      float* const zbase = keep ? a.dz[l - 1] : a.partial + (int64_t)blockIdx.x * bwd_slab_floats(kH, L);
+      float* const zbase = keep ? a.dz[l - 1] : a.partial + (int64_t)blockIdx.x * SirenBwdSlab{kH, L}.floats();
       const int tmul = keep ? 1 : 0;
       int64_t zoff[2];
 #pragma unroll
@@ -1033,9 +1035,10 @@ __global__ __launch_bounds__(kThreadsR) void siren_backward_rows_kernel(const Bw
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   RP_END_TO(g_rows_profile_bwd)
 
-  // ---- this workgroup's slab: dW_head [H] | db_head [4] | db_l [L][H] | dW_first [H][kMaxIn] ---------------------------------
+  // ---- this workgroup's slab (SirenBwdSlab) ------------------------------------------------------------------------------
   // (head weight and head bias: the forward kernel's; zeros here)
-  float* slab = a.partial + (int64_t)blockIdx.x * bwd_slab_floats(kH, L);
+  const SirenBwdSlab lay{kH, L};
+  float* slab = a.partial + (int64_t)blockIdx.x * lay.floats();
   __syncthreads();
   float* red = reinterpret_cast<float*>(&sm.ring[0][0]);  // [wave][4 inputs + last bias][H]
 #pragma unroll
@@ -1048,13 +1051,13 @@ __global__ __launch_bounds__(kThreadsR) void siren_backward_rows_kernel(const Bw
   __syncthreads();
   {
     const int f = tid;  // 256 threads = H
-    slab[f] = 0.f;
-    if (f < 4) slab[kH + f] = 0.f;
-    float* p_b = slab + kH + 4;
+    lay.w_head(slab)[f] = 0.f;
+    if (f < 4) lay.b_head(slab)[f] = 0.f;
+    float* p_b = lay.b(slab, 0);
     for (int l = 0; l + 1 < L; ++l)
       p_b[l * kH + f] = ((sm.gb[l][0][f] + sm.gb[l][1][f]) + sm.gb[l][2][f]) + sm.gb[l][3][f];
     p_b[(L - 1) * kH + f] = ((red[(0 * 5 + 4) * kH + f] + red[(1 * 5 + 4) * kH + f]) + red[(2 * 5 + 4) * kH + f]) + red[(3 * 5 + 4) * kH + f];
-    float* p_wf = p_b + L * kH;
+    float* p_wf = lay.w_first(slab);
 #pragma unroll
     for (int d = 0; d < kMaxIn; ++d)
       p_wf[f * kMaxIn + d] =
@@ -1070,7 +1073,7 @@ int rows_blocks(int64_t n) { return (int)std::min<int64_t>(ceil_div(n, rr::kRows
 bool rows_supported(int hidden, int n_sine) { return hidden == rr::kH && n_sine >= 2; }
 // dLoss/dy per row between the loss-mode forward and the backward kernel: behind both kernels' slabs in the slab region
 int64_t rows_dy_offset(int64_t n, int hidden, int n_sine) {
-  const int64_t slabs = (int64_t)rows_blocks(n) * std::max(fwd_slab_floats(hidden), bwd_slab_floats(hidden, n_sine)) * 4;
+  const int64_t slabs = (int64_t)rows_blocks(n) * std::max(SirenFwdSlab{hidden}.floats(), SirenBwdSlab{hidden, n_sine}.floats()) * 4;
   return (slabs + 255) / 256 * 256;
 }
 

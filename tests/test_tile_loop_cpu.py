@@ -17,7 +17,7 @@ def lib():
 @pytest.mark.parametrize("hidden", sorted(SIREN_ROWS))
 def test_siren_tile_rows_are_the_librarys(lib, hidden):
     """One sine layer has no weight-gradient term: mri_siren_backward_workspace_bytes(n, hidden, 1) is chain_blocks x
-    bwd_slab_floats rounded to 256 bytes (siren_chain.hip slab_region_bytes), chain_blocks = min(ceil(n / R), 256).  So
+    SirenBwdSlab::floats() rounded to 256 bytes (siren_chain.hip slab_region_bytes), chain_blocks = min(ceil(n / R), 256).  So
     it still grows from n = 255 R to 256 R and no longer from there.  A table entry below the library's R is still
     under the cap at 256 R, where one more row adds a workgroup: the equalities fail.  An entry above it is at the cap
     at 255 R already: the inequality fails."""

@@ -46,6 +46,8 @@ for w in ("cfg3", "cfg4", "cfg4_packed", "cfg2", "cfg5"):
         # bin_kernel<.., false> the count) are ADDED -- round 2 overwrote one with the other
         key = re.sub(r"<.*", "", r["kernel"])
         mb[key] = mb.get(key, 0.0) + float(r["hbm_mb_corrected"])
+        if key == "slab_reduce_kernel":  # its instances serve different phases: kept apart as well
+            mb[r["kernel"]] = float(r["hbm_mb_corrected"])
     traffic[w] = mb
 
 
@@ -99,8 +101,10 @@ for name in ("cfg4", "cfg4_packed", "cfg2", "cfg5"):
 split = t3.get("siren_split_weights_kernel", 0) / 2  # launched by the forward and by the backward entry
 fwd3 = next(v for k, v in t3.items() if k.startswith("siren_forward"))    # siren_forward_rows_kernel (H = 256) / siren_forward_kernel
 bwd3 = next(v for k, v in t3.items() if k.startswith("siren_backward"))
-d["cfg3"] = {"mlp_fwd": int((fwd3 + t3.get("siren_fwd_reduce_kernel", 0) + split) * 1e6),
-             "mlp_bwd": int((bwd3 + t3.get("siren_bwd_reduce_kernel", 0) + split +
+# slab_reduce_kernel<G, segments of the table>: <1, 4> behind the loss-mode forward (SirenFwdSlab::kSegments), <1, 11> behind
+# the backward (SirenBwdSlab::kSegments)
+d["cfg3"] = {"mlp_fwd": int((fwd3 + t3.get("slab_reduce_kernel<1, 4>", 0) + split) * 1e6),
+             "mlp_bwd": int((bwd3 + t3.get("slab_reduce_kernel<1, 11>", 0) + split +
                              4 * (t3["siren_wgrad_kernel"] + t3.get("slab_sum_kernel", 0))) * 1e6),
              "adam": int(t3["adam_kernel"] * 1e6)}
 json.dump(d, open(tj, "w"), indent=2)
