@@ -570,6 +570,39 @@ int mri_modsiren_gradient(const float* x, int64_t n, int32_t dim_in, int32_t hid
                           const float* const* mod_weight, const float* const* mod_bias, float w0_first, float w0,
                           float* y, float* dydx, void* workspace, int64_t workspace_bytes, void* stream);
 
+/* ---- RffNet: Gaussian Fourier features and a ReLU MLP (csrc/rff.hip) ------------------------
+ * (reference models.py:542-584.)  rff.layers.GaussianEncoding holds a frozen b (n_freq, dim_in) and computes
+ * vp = (fl32(2 pi) x) b^T -- the coordinates are scaled first, then multiplied -- and z = [cos(vp) | sin(vp)],
+ * cosines first.  Sine and cosine are correct for every finite argument: the Cody-Waite fast path up to |vp| = 8192,
+ * the library's full-range sincosf beyond.  Every buffer is contiguous row-major and accessed 4 bytes at a time at
+ * any 4-byte aligned address; nothing is written beyond row n; n = 0 returns 0 without a launch.
+ * mri_rff_encode (models.py:542-584, the encoder): z (n, 2 n_freq).  1 <= dim_in <= 8, n_freq >= 1.
+ * mri_rff_encode_backward_input (models.py:542-584, autograd of the encoder with respect to x):
+ *   dx[i, d] = fl32(2 pi) sum_f b[f, d] (cos(vp_f) dz[i, n_freq + f] - sin(vp_f) dz[i, f]),
+ *   one wave per row, summed in a fixed order: no atomics, bitwise reproducible.  b gets no gradient (it is frozen). */
+int mri_rff_encode(const float* x, int64_t n, int32_t dim_in, const float* b, int32_t n_freq, float* z, void* stream);
+int mri_rff_encode_backward_input(const float* x, int64_t n, int32_t dim_in, const float* b, int32_t n_freq,
+                                  const float* dz, float* dx, void* stream);
+/* Inference of the whole network (models.py:542-584: the encoder, then `decoder`, n_layers Linears
+ * 2 n_freq -> hidden -> ... -> hidden -> 1 with ReLU behind EVERY one, the last included) in ONE persistent kernel:
+ * the VALU encodes a row tile into two f32 LDS images (cos, sin) -- z is never written, 8 n_freq bytes of HBM
+ * traffic per point saved each way --; the first Linear is two hidden x hidden products, W_0[:, :n_freq] on the cos
+ * image and W_0[:, n_freq:] on the sin image, into one accumulator on the bf16 matrix pipe with three-term operands
+ * (f32-accurate); Linears 1 .. n_layers - 2 are one product each; bias and ReLU are the epilogue; the head is a dot
+ * product per row, plus bias, then ReLU: y (n) >= 0.  512 threads, at most 256 workgroups, tiles of 64 rows at
+ * hidden 128 and 128 rows at hidden 64.  Fixed summation order: two calls agree bitwise.
+ * Supported (mri_rff_forward_supported is the truth): hidden 64 / 128, n_freq == hidden, 1 <= dim_in <= 4,
+ * 2 <= n_layers <= 8, dim_out 1, a bias on every Linear; anything else is refused with MRI_ERR_INVALID_ARGUMENT, the
+ * offending argument named in mri_last_error.  weight / bias: HOST arrays of n_layers device pointers ([0] (hidden,
+ * 2 n_freq), [1 .. n_layers-2] (hidden, hidden), [n_layers-1] (1, hidden)).  workspace:
+ * mri_rff_forward_workspace_bytes device bytes (the split weights: n_layers hidden x hidden matrices in three bf16
+ * terms; -1 for an unsupported width or depth), 16-byte aligned; its contents on entry do not matter. */
+int mri_rff_forward_supported(int32_t dim_in, int32_t hidden, int32_t n_freq, int32_t n_layers, int32_t dim_out);
+int64_t mri_rff_forward_workspace_bytes(int32_t hidden, int32_t n_layers);
+int mri_rff_forward(const float* x, int64_t n, int32_t dim_in, int32_t hidden, int32_t n_freq, int32_t n_layers,
+                    const float* b, const float* const* weight, const float* const* bias, float* y, void* workspace,
+                    int64_t workspace_bytes, void* stream);
+
 /* ---- PsfSirenNet: the acquisition point-spread function -----------------------------------
  * (reference models.py:397-539.)  A target voxel b is the network averaged over S sample points around it:
  * rows b*S + k of the expanded batch hold x[b] + offsets[k], and the voxel value is sum_k w_k z[b*S + k]

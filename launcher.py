@@ -47,6 +47,8 @@ def parse_args(argv=None):
                    help="hash grid: one integer, or one per axis, e.g. 16,16,5,7 (per-axis values "
                         "select MultiResHashGridV2, as in reference models.py:691-708)")
     p.add_argument("--finest_resolution", type=str, help="as --base_resolution (floats allowed)")
+    p.add_argument("--n_frequencies", type=int, help="RffNet: Gaussian Fourier frequencies (features: twice as many)")
+    p.add_argument("--sigma", type=float, help="RffNet: standard deviation of the frozen Gaussian projection")
     p.add_argument("--tiny_mlp", action="store_true",
                    help="HashMLP with the fused ReLU tiny-MLP decoder of hash_config.json")
     p.add_argument("--fused_batchnorm", action="store_true",
@@ -154,6 +156,8 @@ def build_model(config, models):
             batch_norm=config.batch_norm)
         everything.pop("final_activation")
         everything["final_activation"] = config.final_activation_on
+    if config.model_class == "RffNet":
+        everything.update(n_frequencies=config.n_frequencies, sigma=config.sigma)
     if config.model_class == "PsfSirenNet":
         spacing = getattr(config, "coordinates_spacing", None)
         if spacing is None:

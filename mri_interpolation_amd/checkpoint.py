@@ -34,6 +34,8 @@ def _dead_base_stack(model) -> "OrderedDict[str, torch.Tensor]":
     (what Lightning would have saved: never trained)."""
     out = OrderedDict()
     n_layers = int(getattr(model, "n_layers", 0))
+    if type(model).__name__ == "RffNet":  # `super().__init__()` without arguments (models.py:554): BaseMLP's own 8
+        n_layers = 8
     # a forked, seeded generator: saving neither advances the caller's RNG nor depends on it
     with torch.random.fork_rng(devices=[]):
         torch.manual_seed(1337)
@@ -48,7 +50,8 @@ def reference_state_dict(model) -> "OrderedDict[str, torch.Tensor]":
     """model.state_dict() on the CPU with the keys, in the order, the reference module of the same class
     holds (HashMLP: the dead `layers.*` entries first, as `BaseMLP.__init__` registers them first)."""
     sd = OrderedDict((k, v.detach().cpu().clone()) for k, v in model.state_dict().items())
-    if type(model).__name__ == "HashMLP":
+    if type(model).__name__ in ("HashMLP", "RffNet"):  # (RffNet's frozen `encoder.b` is a parameter there too: Adam
+        # numbers it and never holds state for it)
         sd = OrderedDict(list(_dead_base_stack(model).items()) + list(sd.items()))
     return sd
 

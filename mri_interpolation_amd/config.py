@@ -41,6 +41,9 @@ class BaseConfig:
     slice_spec: Optional[str] = None  # e.g. ":,:,3,7" -> train on a sub-volume
     enco_config: Optional[dict] = None
     log: str = ""
+    # RffNet (reference models.py:549-550)
+    n_frequencies: int = 128
+    sigma: float = 10.0
 
     def resolve(self, volume_shape: Sequence[int]):
         self.image_shape = tuple(int(s) for s in volume_shape)

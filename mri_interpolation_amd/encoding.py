@@ -199,3 +199,25 @@ class Frequency(nn.Module):
     def forward(self, x: torch.Tensor):
         return ops.FrequencyFunction.apply(x, self.n_levels)
 
+
+class GaussianEncoding(nn.Module):
+    """Gaussian random Fourier features with the surface of `rff.layers.GaussianEncoding` as the reference's RffNet
+    uses it (models.py:565-567): a frozen `b = randn(encoded_size, input_size) * sigma` (state-dict key `b`,
+    requires_grad False), `forward(v) = cat(cos(vp), sin(vp))` with `vp = 2 * pi * v @ b.T`, i.e. the coordinates are
+    scaled by fl32(2 pi) first, then multiplied; cosines first.  One HIP kernel forward, one for the gradient with
+    respect to v (csrc/rff.hip)."""
+
+    def __init__(self, sigma: float = None, input_size: int = None, encoded_size: int = None, b: torch.Tensor = None):
+        super().__init__()
+        if b is None:
+            if sigma is None or input_size is None or encoded_size is None:
+                raise ValueError('Arguments "sigma," "input_size," and "encoded_size" are required.')
+            b = torch.randn((encoded_size, input_size)) * sigma
+        elif sigma is not None or input_size is not None or encoded_size is not None:
+            raise ValueError('Only specify the "b" argument when using it.')
+        self.b = nn.Parameter(b.detach().clone().float(), requires_grad=False)
+        self.input_dim = self.b.shape[1]
+        self.output_dim = 2 * self.b.shape[0]
+
+    def forward(self, v: torch.Tensor) -> torch.Tensor:
+        return ops.rff_encode(v, self.b)

@@ -3,6 +3,7 @@
 Mirrors reference `models.py`: `BaseMLP` (models.py:20-95), `Sine` (:108-114), `SirenLayer`
 (:117-156), `SirenNet` (:160-233), `Modulator` / `ModulatedSirenNet` (:236-322), `HashMLP` (:658-754): same constructor arguments,
 `PsfSirenNet` (:397-539): same constructor arguments,
+`RffNet` (:542-584): same constructor arguments,
 `forward(x)`, `training_step`, `predict_step`, `configure_optimizers`, same state-dict keys.
 Known defects of the reference are resolved to the INTENDED semantics:
   Q1  HashMLP.forward applies the decoder blocks in sequence (the reference calls a ModuleList);
@@ -456,6 +457,80 @@ class HashMLP(BaseMLP):
     def _load_from_state_dict(self, state_dict, prefix, local_metadata, strict, missing_keys,
                               unexpected_keys, error_msgs):
         # Q3: reference checkpoints carry BaseMLP's dead default stack under `layers.*`
+        for key in [k for k in state_dict if k.startswith(prefix + "layers.")]:
+            state_dict.pop(key)
+        super()._load_from_state_dict(state_dict, prefix, local_metadata, strict, missing_keys,
+                                      unexpected_keys, error_msgs)
+
+
+class RffNet(BaseMLP):
+    """Gaussian Fourier-feature MLP (reference models.py:542-584): a frozen projection `encoder.b`, [cos | sin]
+    features, then `decoder`, n_layers Linears 2 n_frequencies -> dim_hidden -> ... -> dim_out with the activation
+    behind EVERY one, the last included (with ReLU the output is clamped at 0).  State-dict keys `encoder.b` and
+    `decoder.{2i}.weight/bias`.  Like HashMLP (Q3) the class does not build BaseMLP's unused default `layers` stack;
+    checkpoints that carry those dead `layers.*` keys still load.  Coordinates in [0, 1].
+    `forward` is the encoding op and the layer ops (differentiable: training_step + autograd, and
+    forward_with_gradient through the encoder's input gradient).  Inference -- `predict_step`, and `forward` under
+    torch.no_grad() in eval mode -- runs ONE kernel (ops.rff_forward, csrc/rff.hip) where `_inference_plan` finds it
+    serves; `fused_inference=False` keeps inference on the layer path."""
+
+    def __init__(self, dim_in: int, dim_hidden: int = 128, dim_out: int = 1, n_layers: int = 8,
+                 n_frequencies: int = 128, sigma: float = 10.0, activation=nn.ReLU, lr: float = 1e-4,
+                 fused_inference: bool = True):
+        super().__init__(dim_in=dim_in, dim_out=dim_out, dim_hidden=dim_hidden, n_layers=n_layers,
+                         activation=activation, lr=lr, _build_layers=False)
+        self.n_frequencies = n_frequencies
+        self.sigma = sigma
+        self.fused_inference = fused_inference
+        self.encoder = encoding.GaussianEncoding(sigma=sigma, input_size=dim_in, encoded_size=n_frequencies)
+        self.decoder = self._make_stack(2 * n_frequencies, dim_hidden, dim_out, n_layers, activation,
+                                        final_activation=True)
+
+    def forward(self, x):
+        if not torch.is_grad_enabled() and not self.training:
+            plan = self._inference_plan(x)
+            if plan is not None:
+                return ops.rff_forward(x, **plan)
+        return self.decoder(self.encoder(x))
+
+    def predict_step(self, batch, batch_idx):
+        x, y = batch
+        plan = self._inference_plan(x)
+        if plan is not None:
+            with torch.no_grad():
+                return ops.rff_forward(x.detach(), **plan)
+        return self(x)
+
+    def _inference_plan(self, x):
+        """Arguments of the fused inference kernel, or None where the layer path serves: a float32 (n, dim_in) tensor
+        on the GPU, ReLU fused into every Linear, biases everywhere, a shape the kernel takes."""
+        if not self.fused_inference or not x.is_cuda or x.dtype != torch.float32 or x.dim() != 2:
+            return None
+        linears = [m for m in self.decoder if isinstance(m, nn.Linear)]
+        if len(linears) * 2 != len(self.decoder) or any(not isinstance(m, FusedLinear) for m in linears):
+            return None  # (an activation without a fused epilogue runs as its own module)
+        if any(m.activation_code != ops.ACT_RELU or m.bias is None for m in linears):
+            return None
+        b = self.encoder.b
+        n_freq, dim_in = b.shape
+        hidden = linears[0].weight.shape[0]
+        if x.shape[1] != dim_in or linears[0].weight.shape != (hidden, 2 * n_freq) \
+                or any(m.weight.shape != (hidden, hidden) for m in linears[1:-1]) \
+                or linears[-1].weight.shape != (1, hidden) or len(linears) < 2:
+            return None
+        if not ops.rff_forward_supported(dim_in, hidden, n_freq, len(linears), self.dim_out):
+            return None
+        return dict(b=b.detach(), weights=[m.weight.detach() for m in linears],
+                    biases=[m.bias.detach() for m in linears])
+
+    def configure_optimizers(self):
+        # torch.optim.Adam skips encoder.b (it never has a gradient); the flat buffers never take it
+        self.optimizer = optim.Adam([p for p in self.parameters() if p.requires_grad], lr=self.lr)
+        return self.optimizer
+
+    def _load_from_state_dict(self, state_dict, prefix, local_metadata, strict, missing_keys,
+                              unexpected_keys, error_msgs):
+        # reference checkpoints carry BaseMLP's dead default stack under `layers.*` (Q3)
         for key in [k for k in state_dict if k.startswith(prefix + "layers.")]:
             state_dict.pop(key)
         super()._load_from_state_dict(state_dict, prefix, local_metadata, strict, missing_keys,

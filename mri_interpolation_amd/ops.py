@@ -422,6 +422,107 @@ class FrequencyFunction(torch.autograd.Function):
         return dx.reshape(ctx.shape), None
 
 
+# --------------------------------------------------------------------------- Gaussian Fourier features (RffNet)
+def rff_encode_forward(x, b, out=None):
+    """z (n, 2F) = [cos(vp) | sin(vp)], vp = (fl32(2 pi) x) b^T (csrc/rff.hip); b (F, dim_in)."""
+    _gpu(x, b, out)
+    x, b = _rowmajor(x).contiguous(), b.contiguous()
+    n, dim_in = x.shape
+    if b.dim() != 2 or b.shape[1] != dim_in:
+        raise ValueError(f"rff_encode: b is (n_frequencies, dim_in = {dim_in}), got {tuple(b.shape)}")
+    if out is None:
+        out = torch.empty((n, 2 * b.shape[0]), device=x.device, dtype=torch.float32)
+    if tuple(out.shape) != (n, 2 * b.shape[0]) or not out.is_contiguous():
+        raise ValueError("rff_encode: out is contiguous (n, 2 n_frequencies)")
+    _lib.call("mri_rff_encode", _ptr(x), n, dim_in, _ptr(b), b.shape[0], _ptr(out), _stream())
+    return out
+
+
+def rff_encode_backward_input(x, b, d_out, dx=None):
+    """dx (n, dim_in) of rff_encode_forward from d_out (n, 2F): one wave per row, a fixed summation order."""
+    _gpu(x, b, d_out, dx)
+    x, b, d_out = _rowmajor(x).contiguous(), b.contiguous(), _rowmajor(d_out).contiguous()
+    n, dim_in = x.shape
+    if tuple(d_out.shape) != (n, 2 * b.shape[0]):
+        raise ValueError("rff_encode_backward_input: d_out is (n, 2 n_frequencies)")
+    if dx is None:
+        dx = torch.empty((n, dim_in), device=x.device, dtype=torch.float32)
+    if tuple(dx.shape) != (n, dim_in) or not dx.is_contiguous():
+        raise ValueError("rff_encode_backward_input: dx is contiguous (n, dim_in)")
+    _lib.call("mri_rff_encode_backward_input", _ptr(x), n, dim_in, _ptr(b), b.shape[0], _ptr(d_out), _ptr(dx),
+              _stream())
+    return dx
+
+
+class RffEncodeFunction(torch.autograd.Function):
+    """The frozen projection b gets no gradient (reference: requires_grad=False)."""
+
+    @staticmethod
+    def forward(ctx, x, b):
+        x2 = _rowmajor(x.reshape(-1, x.shape[-1])).contiguous()
+        ctx.save_for_backward(x2, b)
+        ctx.shape = x.shape
+        return rff_encode_forward(x2, b).reshape(*x.shape[:-1], 2 * b.shape[0])
+
+    @staticmethod
+    def backward(ctx, d_out):
+        x2, b = ctx.saved_tensors
+        if not ctx.needs_input_grad[0]:
+            return None, None
+        dx = rff_encode_backward_input(x2, b, d_out.reshape(x2.shape[0], -1))
+        return dx.reshape(ctx.shape), None
+
+
+def rff_encode(x, b):
+    """Differentiable with respect to x (RffEncodeFunction)."""
+    return RffEncodeFunction.apply(x, b)
+
+
+def rff_forward_supported(dim_in: int, hidden: int, n_frequencies: int, n_layers: int, dim_out: int) -> bool:
+    return bool(_lib.load().mri_rff_forward_supported(dim_in, hidden, n_frequencies, n_layers, dim_out))
+
+
+_rff_ws = {}
+
+
+def rff_forward(x, b, weights, biases, y=None):
+    """y (n, 1) = RffNet(x), ReLU behind every Linear, in one persistent kernel (csrc/rff.hip): the encoding lives in
+    two LDS images, nothing (n, hidden)-sized is written.  weights / biases: the decoder's Linears, the head last."""
+    _gpu(x, b, y, *weights, *biases)
+    x = _rowmajor(x).contiguous()
+    n, dim_in = x.shape
+    n_layers, hidden = len(weights), weights[0].shape[0]
+    if len(biases) != n_layers or n_layers < 2:
+        raise ValueError("rff_forward: at least two Linears, one bias per weight")
+    # the library sees pointers only: a mismatched shape would be read out of bounds on the device
+    if b.dim() != 2 or b.shape[1] != dim_in:
+        raise ValueError(f"rff_forward: b is (n_frequencies, dim_in = {dim_in}), got {tuple(b.shape)}")
+    want = [(hidden, 2 * b.shape[0])] + [(hidden, hidden)] * (n_layers - 2) + [(1, hidden)]
+    for i, (w, v, shape) in enumerate(zip(weights, biases, want)):
+        if tuple(w.shape) != shape or tuple(v.shape) != (shape[0],):
+            raise ValueError(f"rff_forward: Linear {i} is {shape} with a bias of {shape[0]}, got {tuple(w.shape)} and "
+                             f"{tuple(v.shape)}")
+    if y is None:
+        y = torch.empty((n, 1), device=x.device, dtype=torch.float32)
+    if y.numel() != n:
+        raise ValueError("rff_forward: y holds n values")
+    for t in [b, y] + list(weights) + list(biases):
+        if not t.is_contiguous() or t.dtype != torch.float32:
+            raise ValueError("rff_forward needs contiguous float32 parameters and buffers")
+    need = _lib.load().mri_rff_forward_workspace_bytes(hidden, n_layers)
+    ws = _rff_ws.get(x.device.index)
+    if need > 0 and (ws is None or ws.numel() * 4 < need):
+        if ws is not None:
+            torch.cuda.synchronize(x.device)
+        ws = torch.empty((need + 3) // 4, dtype=torch.float32, device=x.device)
+        _rff_ws[x.device.index] = ws
+    if ws is None:  # (the library refuses the shape with its reason)
+        ws = torch.empty(64, dtype=torch.float32, device=x.device)
+    _lib.call("mri_rff_forward", _ptr(x), n, dim_in, hidden, b.shape[0], n_layers, _ptr(b), _ptr_array(weights),
+              _ptr_array(biases), _ptr(y), _ptr(ws), ws.numel() * 4, _stream())
+    return y
+
+
 # --------------------------------------------------------------------------- fused tiny MLP
 def tiny_mlp_supported(k_in: int, hidden: int, dim_out: int) -> bool:
     return bool(_lib.load().mri_tiny_mlp_supported(k_in, hidden, dim_out))
