@@ -602,6 +602,46 @@ int64_t mri_rff_forward_workspace_bytes(int32_t hidden, int32_t n_layers);
 int mri_rff_forward(const float* x, int64_t n, int32_t dim_in, int32_t hidden, int32_t n_freq, int32_t n_layers,
                     const float* b, const float* const* weight, const float* const* bias, float* y, void* workspace,
                     int64_t workspace_bytes, void* stream);
+/* ---- RffNet: fused training step (csrc/rff.hip) ---------------------------------------------
+ * Forward with the loss and the backward chain of the same network, in place of training_step + autograd over the
+ * layer ops (models.py:542-584 RffNet.forward; models.py:61-66 training_step: F.mse_loss).  Notation: Linears
+ * 0 .. L-1 (L = n_layers), z = [c | s], a_0 = relu(z W_0^T + b_0), ..., a_{L-2}, p = a_{L-2} . w_head + b_head,
+ * y = relu(p).  b is frozen: no gradient with respect to b or x.  z (n, 2 n_freq) exists in HBM in NEITHER call.
+ * mri_rff_train_supported (models.py:542-584; models.py:61-66): exactly what mri_rff_forward_supported accepts.
+ * mri_rff_backward_workspace_bytes (models.py:542-584; models.py:61-66): ONE size for both calls, -1 for an
+ *   unsupported width or depth or n outside 1 .. 2^31 - 1.  With G = min(ceil(n / rows), 256) chain workgroups (rows =
+ *   64 at hidden 128, 128 at hidden 64), slab = hidden + 4 + (n_layers - 1) hidden floats, and Wg = min(ceil(n / 32),
+ *   256) * (hidden == 64 ? 2 : 1) weight-gradient slabs of hidden^2 floats:
+ *     bytes = round_up_256(4 max(G slab, 256, 2 Wg hidden^2)) + (2 n_layers - 2) * 6 hidden^2
+ *   (the slabs; the n_layers forward splits and the n_layers - 2 transposed splits in three bf16 terms).  It does not
+ *   grow with n once n fills 256 workgroups.  16-byte aligned; its contents on entry do not matter.
+ * mri_rff_forward_loss (models.py:542-584; models.py:61-66): mri_rff_forward's kernel in its training form.  y (n) is
+ *   bitwise mri_rff_forward's.  act: HOST array of n_layers - 1 device pointers to (n, hidden) row-major, 16-byte
+ *   aligned buffers that receive a_0 .. a_{L-2}, each written once; nothing beyond row n.  dy (n) =
+ *   (y > 0) ? 2 (y - target) / (n_total grad_divisor) : 0, that is dLoss/dp with the head's ReLU applied (ReLU'(0) = 0,
+ *   as torch).  loss_out[0] += sum (y - target)^2 / n_total (n <= n_total: a slice of a batch, as
+ *   mri_modsiren_forward_loss), the workgroups' shares added in a fixed order.
+ * mri_rff_backward (models.py:542-584; models.py:61-66, autograd from dy): one persistent kernel walks the Linears
+ *   from the head down with dz_l = da_l (.) [a_l > 0] in ONE LDS image and da_{l-1} = dz_l W_l on the bf16 matrix pipe
+ *   (three-term operands); dz: HOST array of n_layers - 1 device pointers to (n, hidden) 16-byte aligned scratch, each
+ *   written once.  dW_l (l = 1 .. L-2) = dz_l^T a_{l-1}: the SIREN chain's weight-gradient kernel.  dW_0 =
+ *   [dz_0^T c | dz_0^T s]: a kernel of its own that recomputes c and s from x and b as the forward computes them.
+ *   Bias and head gradients are summed per workgroup; all partial sums meet in `workspace` and are added in a fixed
+ *   order: no float atomics, bitwise reproducible.  d_weight / d_bias (n_layers pointers each): gradients are ADDED.
+ * Both calls validate every argument before any pointer reaches the device (NULLs, the alignment of act / dz /
+ * workspace, ranges including n <= n_total, a short workspace, unsupported shapes: MRI_ERR_INVALID_ARGUMENT with the
+ * offending argument named in mri_last_error).  n = 0 returns 0 without a launch.  Every other pointer: any 4-byte
+ * aligned address.  weight / bias as mri_rff_forward. */
+int mri_rff_train_supported(int32_t dim_in, int32_t hidden, int32_t n_freq, int32_t n_layers, int32_t dim_out);
+int64_t mri_rff_backward_workspace_bytes(int64_t n, int32_t hidden, int32_t n_layers);
+int mri_rff_forward_loss(const float* x, const float* target, int64_t n, int64_t n_total, int32_t dim_in,
+                         int32_t hidden, int32_t n_freq, int32_t n_layers, const float* b, const float* const* weight,
+                         const float* const* bias, float grad_divisor, float* const* act, float* y, float* dy,
+                         float* loss_out, void* workspace, int64_t workspace_bytes, void* stream);
+int mri_rff_backward(const float* x, const float* dy, int64_t n, int32_t dim_in, int32_t hidden, int32_t n_freq,
+                     int32_t n_layers, const float* b, const float* const* weight, const float* const* act,
+                     float* const* dz, float* const* d_weight, float* const* d_bias, void* workspace,
+                     int64_t workspace_bytes, void* stream);
 
 /* ---- PsfSirenNet: the acquisition point-spread function -----------------------------------
  * (reference models.py:397-539.)  A target voxel b is the network averaged over S sample points around it:

@@ -59,6 +59,10 @@ def parse_args(argv=None):
                    help="ModulatedSirenNet: train and predict through the fused modulated SIREN kernel chain "
                         "(both stacks of a row tile on chip) instead of training_step + autograd; with "
                         "--save_gradient the gradient volumes come from the fused modulated gradient kernel")
+    p.add_argument("--fused_rff", action="store_true",
+                   help="RffNet: train and predict through the fused RFF kernel chain (encoding, every Linear and "
+                        "the loss of a row tile in one kernel, one backward chain kernel) instead of training_step + "
+                        "autograd; needs n_frequencies == dim_hidden in {64, 128}, else the autograd path stays")
     p.add_argument("--no_batchnorm", action="store_true",
                    help="HashMLP without the BatchNorm1d of its decoder blocks, GELU kept (the notebook's decoder, "
                         "Linear -> GELU twice): trains through the one-kernel shallow decoder step")
@@ -262,7 +266,8 @@ def main(argv=None):
     trainer = Trainer(max_epochs=config.epochs, max_steps=args.max_steps, precision=32,
                       log_every=args.log_every,
                       accumulate_grad_batches=config.accumulate_grad_batches,
-                      fused_batchnorm=args.fused_batchnorm, fused_modulated=args.fused_modulated)
+                      fused_batchnorm=args.fused_batchnorm, fused_modulated=args.fused_modulated,
+                      fused_rff=args.fused_rff)
     t0 = time.time()
     trainer.fit(model, train_loader)
     train_seconds = time.time() - t0

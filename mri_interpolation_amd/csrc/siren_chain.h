@@ -81,6 +81,12 @@ int split_weights_ld(const float* const* w, int count, int hidden, int ld, bool 
 // dW[:, :H] += dz^T act, summed over the slabs in a fixed order into a row-major matrix of row stride `ld` floats
 int wgrad_any_ld(int hidden, const WgradArgs& g, float* d_weight, int ld, hipStream_t st);
 int64_t wgrad_slab_floats(int64_t n, int hidden);  // floats of WgradArgs::partial
+// ... for rff.hip, whose first Linear's weight gradient has a kernel of its own on the same plan: the slab geometry
+// (workgroups for n rows, slabs per workgroup) and slab_sum_kernel's launch: to += the `slabs` slabs of `count` floats
+// at `partial`, in the tree order of slab.h
+int wgrad_blocks(int64_t n);
+int wgrad_split(int hidden);
+int sum_wgrad_slabs(const float* partial, int slabs, int count, const SlabDest& to, hipStream_t st);
 
 // ---- host-side helpers of the entry points -----------------------------------------------------------------------
 // f(std::integral_constant<int, H>) for the hidden width of a plain chain (32 / 64 / 128 / 256, checked by the caller)

@@ -814,9 +814,7 @@ bool chain_supported(int dim_in, int hidden, int n_sine, int dim_out) {
 }
 
 int tile_rows(int hidden) { return hidden >= 256 ? 64 : hidden == 128 ? 128 : 256; }
-int wgrad_split(int hidden) { return hidden >= 128 ? 1 : hidden == 64 ? 2 : 8; }
 int chain_blocks(int hidden, int64_t n) { return (int)std::min<int64_t>(ceil_div(n, tile_rows(hidden)), 256); }
-int wgrad_blocks(int64_t n) { return (int)std::min<int64_t>(ceil_div(n, kWr), 256); }
 
 template <int H>
 int launch_forward(const ChainArgs& a, int mode, hipStream_t st) {
@@ -878,6 +876,13 @@ int split_weights_ld(const float* const* w, int count, int hidden, int ld, bool 
 
 int wgrad_any_ld(int hidden, const WgradArgs& g, float* d_weight, int ld, hipStream_t st) {
   return dispatch_hidden(hidden, [&](auto h) { return launch_wgrad<decltype(h)::value>(g, d_weight, st, ld); });
+}
+
+int wgrad_split(int hidden) { return hidden >= 128 ? 1 : hidden == 64 ? 2 : 8; }
+int wgrad_blocks(int64_t n) { return (int)std::min<int64_t>(ceil_div(n, kWr), 256); }
+int sum_wgrad_slabs(const float* partial, int slabs, int count, const SlabDest& to, hipStream_t st) {
+  hipLaunchKernelGGL(slab_sum_kernel, dim3((unsigned)ceil_div(count, 256)), dim3(256), 0, st, partial, slabs, count, to);
+  return check_launch("slab_sum_kernel");
 }
 
 int64_t wgrad_slab_floats(int64_t n, int hidden) {

@@ -84,6 +84,16 @@ struct ModBwdSlab {
   MRI_SLAB_FIELD b_head(P p) const { return w_head(p) + H; }
   __host__ __device__ int floats() const { return b_head(0) + 4; }
 };
+
+// RffNet backward (rff.hip), L Linears: dW_head [H] | db_head (padded to 4) | db_l [L-1][H], l = 0 .. L-2
+struct RffBwdSlab {
+  int H, L;
+  static constexpr int kSegments = kMaxSine + 1;      // L <= kMaxSine
+  MRI_SLAB_FIELD w_head(P p) const { return p; }
+  MRI_SLAB_FIELD b_head(P p) const { return w_head(p) + H; }
+  MRI_SLAB_FIELD b(P p, int l) const { return b_head(p) + 4 + l * H; }
+  __host__ __device__ int floats() const { return b(0, L - 1); }
+};
 #undef MRI_SLAB_FIELD
 
 // ---- the segment table: where element e of a summed slab goes ---------------------------------------------------------
@@ -188,6 +198,14 @@ inline SegmentTable<ModBwdSlab::kSegments> segments(const ModBwdSlab& s, int dim
   for (int l = 0; l < s.L; ++l) t.vector(s.bm(0, l), s.H, d_bm[l]);
   for (int l = 0; l < s.L; ++l) t.vector(s.bs(0, l), s.H, d_bs[l]);
   t.vector(s.w_head(0), s.H, d_ws[s.L]), t.vector(s.b_head(0), 1, d_bs[s.L]);
+  return t;
+}
+
+// d_w / d_b: the L Linears of an RffNet; [L-1] is the head (the dW of Linears 0 .. L-2: slab_sum_kernel)
+inline SegmentTable<RffBwdSlab::kSegments> segments(const RffBwdSlab& s, float* const* d_w, float* const* d_b) {
+  SegmentTable<RffBwdSlab::kSegments> t{};
+  t.vector(s.w_head(0), s.H, d_w[s.L - 1]), t.vector(s.b_head(0), 1, d_b[s.L - 1]);
+  for (int l = 0; l + 1 < s.L; ++l) t.vector(s.b(0, l), s.H, d_b[l]);
   return t;
 }
 

@@ -523,6 +523,102 @@ def rff_forward(x, b, weights, biases, y=None):
     return y
 
 
+def rff_train_supported(dim_in: int, hidden: int, n_frequencies: int, n_layers: int, dim_out: int) -> bool:
+    return bool(_lib.load().mri_rff_train_supported(dim_in, hidden, n_frequencies, n_layers, dim_out))
+
+
+def rff_train_workspace(n: int, hidden: int, n_layers: int, device) -> torch.Tensor:
+    """Scratch of rff_forward_loss and rff_backward for batches of up to n rows (partial sums, split weights)."""
+    need = _lib.load().mri_rff_backward_workspace_bytes(max(int(n), 1), hidden, n_layers)
+    if need < 0:
+        raise ValueError(f"fused RFF step: hidden {hidden} x {n_layers} Linears is not supported")
+    return torch.empty((need + 3) // 4, dtype=torch.float32, device=device)
+
+
+_rff_train_ws = {}
+
+
+def _rff_train_scratch(device, n, hidden, n_layers, ws):
+    if ws is not None:  # the caller's own (FusedStep's, one per batch size): the library checks its size
+        _gpu(ws)
+        return ws
+    need = _lib.load().mri_rff_backward_workspace_bytes(max(int(n), 1), hidden, n_layers)
+    if need < 0:  # (the library refuses the shape with its reason)
+        return torch.empty(64, dtype=torch.float32, device=device)
+    ws = _rff_train_ws.get(device.index)
+    if ws is None or ws.numel() * 4 < need:
+        if ws is not None:
+            torch.cuda.synchronize(device)
+        ws = torch.empty((need + 3) // 4, dtype=torch.float32, device=device)
+        _rff_train_ws[device.index] = ws
+    return ws
+
+
+def _rff_train_check(what, x, b, weights, others, per_layer, flat):
+    """What the library cannot see behind its pointers: the shapes of b and the Linears, one (n, hidden) buffer per
+    hidden Linear in each of `per_layer`, n values in each of `flat`; everything contiguous float32."""
+    n, dim_in = x.shape
+    n_layers, hidden = len(weights), weights[0].shape[0]
+    if n_layers < 2 or any(len(o) != n_layers for o in others):
+        raise ValueError(f"{what}: at least two Linears, one bias / gradient per weight")
+    if b.dim() != 2 or b.shape[1] != dim_in:
+        raise ValueError(f"{what}: b is (n_frequencies, dim_in = {dim_in}), got {tuple(b.shape)}")
+    want = [(hidden, 2 * b.shape[0])] + [(hidden, hidden)] * (n_layers - 2) + [(1, hidden)]
+    for i, shape in enumerate(want):
+        if tuple(weights[i].shape) != shape:
+            raise ValueError(f"{what}: Linear {i} is {shape}, got {tuple(weights[i].shape)}")
+        for o in others:
+            if tuple(o[i].shape) not in (shape, (shape[0],)):
+                raise ValueError(f"{what}: Linear {i} takes {shape} / ({shape[0]},) tensors, got {tuple(o[i].shape)}")
+    for name, seq in per_layer.items():
+        if len(seq) != n_layers - 1:
+            raise ValueError(f"{what}: {name} needs one (n, hidden) buffer per hidden Linear")
+        if any(tuple(t.shape) != (n, hidden) for t in seq):
+            raise ValueError(f"{what}: {name} buffers are (n, hidden)")
+    for name, t in flat.items():
+        if t.numel() != n:
+            raise ValueError(f"{what}: {name} holds n values")
+    every = [b] + list(weights) + [t for o in others for t in o] + [t for s in per_layer.values() for t in s] \
+        + list(flat.values())
+    for t in every:
+        if not t.is_contiguous() or t.dtype != torch.float32:
+            raise ValueError(f"{what} needs contiguous float32 parameters and buffers")
+    return n, dim_in, hidden, n_layers
+
+
+def rff_forward_loss(x, target, b, weights, biases, act, y, dy, loss_out, n_total=None, grad_divisor: float = 1.0,
+                     ws=None):
+    """Training forward of an RffNet with mse_loss(y, target) in the same kernel (mri_rff_forward_loss,
+    include/mri_inr.h): act [n_layers - 1] x (n, hidden) receive the hidden activations, dy (n, 1) receives dLoss / dp
+    (the head's ReLU applied), loss_out is ADDED to.  Follow with rff_backward(x, dy, ...)."""
+    _gpu(x, target, b, y, dy, loss_out, ws, *weights, *biases, *act)
+    x = _rowmajor(x).contiguous()
+    target = target.reshape(-1).contiguous()
+    n, dim_in, hidden, n_layers = _rff_train_check("rff_forward_loss", x, b, weights, [biases], dict(act=act),
+                                                   dict(target=target, y=y, dy=dy))
+    if target.dtype != torch.float32 or loss_out.dtype != torch.float32 or loss_out.numel() < 1:
+        raise ValueError("rff_forward_loss needs a float32 target and a float32 loss_out of one element")
+    ws = _rff_train_scratch(x.device, n, hidden, n_layers, ws)
+    _lib.call("mri_rff_forward_loss", _ptr(x), _ptr(target), n, n if n_total is None else n_total, dim_in, hidden,
+              b.shape[0], n_layers, _ptr(b), _ptr_array(weights), _ptr_array(biases), float(grad_divisor),
+              _ptr_array(act), _ptr(y), _ptr(dy), _ptr(loss_out), _ptr(ws), ws.numel() * 4, _stream())
+    return y
+
+
+def rff_backward(x, dy, b, weights, act, dz, d_weights, d_biases, ws=None):
+    """Backward of rff_forward_loss from dy = dLoss / dp (mri_rff_backward): one chain kernel, a slab reduction, one
+    weight-gradient kernel per Linear.  act: what the forward stored; dz [n_layers - 1] x (n, hidden): scratch.
+    Gradients are ADDED to d_weights / d_biases (one per Linear, the head last).  b gets none: it is frozen."""
+    _gpu(x, dy, b, ws, *weights, *act, *dz, *d_weights, *d_biases)
+    x = _rowmajor(x).contiguous()
+    n, dim_in, hidden, n_layers = _rff_train_check("rff_backward", x, b, weights, [d_weights, d_biases],
+                                                   dict(act=act, dz=dz), dict(dy=dy))
+    ws = _rff_train_scratch(x.device, n, hidden, n_layers, ws)
+    _lib.call("mri_rff_backward", _ptr(x), _ptr(dy), n, dim_in, hidden, b.shape[0], n_layers, _ptr(b),
+              _ptr_array(weights), _ptr_array(act), _ptr_array(dz), _ptr_array(d_weights), _ptr_array(d_biases),
+              _ptr(ws), ws.numel() * 4, _stream())
+
+
 # --------------------------------------------------------------------------- fused tiny MLP
 def tiny_mlp_supported(k_in: int, hidden: int, dim_out: int) -> bool:
     return bool(_lib.load().mri_tiny_mlp_supported(k_in, hidden, dim_out))

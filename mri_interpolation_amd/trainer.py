@@ -23,6 +23,11 @@ Opt-in as well: without the flag that model runs `training_step` + autograd over
 The notebook's HashMLP (two blocks Linear -> GELU, no BatchNorm) takes the shallow plan: `train_step` runs its
 decoder -- forward, loss and backward -- as ONE kernel (csrc/mlp_shallow.hip), `forward(train=True)` + `backward()`
 keep the layer kernels.
+RffNet has a chain of its own as well, the RFF plan (`FusedStep(..., rff=True)`, `Trainer(fused_rff=True)`,
+csrc/rff.hip):
+    rff_forward_loss (encoding, every Linear and the loss of a row tile in one kernel) -> rff_backward (one chain
+    kernel, a slab reduction, one weight-gradient kernel per Linear; the encoding is recomputed, never stored) -> adam
+Opt-in too: without the flag that model runs `training_step` + autograd over the HIP ops.
 """
 import contextlib
 import ctypes as C
@@ -119,12 +124,60 @@ def _modulated_plan(model) -> ModulatedPlan:
                          [_Layer(l.weight, l.bias, l._code[0], l._code[1]) for l in siren_modules])
 
 
-def fusable_layers(model, batch_norm: bool = False, modulated: bool = False) -> Optional[tuple]:
+class RffPlan(tuple):
+    """(None, the decoder's Linears in order, the head last) as every plan, with the frozen projection `b`
+    (n_frequencies, dim_in) by name: it is no part of the layers and so of no flat buffer."""
+
+    def __new__(cls, b, layers):
+        self = super().__new__(cls, (None, list(layers)))
+        self.b = b
+        return self
+
+
+def _rff_plan(model) -> RffPlan:
+    """The plan of an RffNet for the training kernels of csrc/rff.hip; ValueError with the reason for what they do
+    not cover (such a model keeps training through training_step + autograd)."""
+    what = "fused RFF step: "
+    modules = list(model.decoder)
+    linears = [m for m in modules if isinstance(m, torch.nn.Linear)]
+    b = model.encoder.b
+    n_freq, dim_in = b.shape
+    if len(linears) < 2 or len(linears) > _lib.MAX_SIREN_LAYERS:
+        raise ValueError(what + f"{len(linears)} Linears (the kernels take 2 .. {_lib.MAX_SIREN_LAYERS})")
+    if len(linears) * 2 != len(modules) or any(not isinstance(m, models.FusedLinear) for m in linears) \
+            or any(m.activation_code != ops.ACT_RELU for m in linears):
+        raise ValueError(what + "an activation other than the fused ReLU behind a Linear "
+                         f"({type(modules[1]).__name__})")
+    if any(m.bias is None for m in linears):
+        raise ValueError(what + "a Linear without a bias (the kernels take biases everywhere)")
+    hidden = linears[0].weight.shape[0]
+    if n_freq != hidden:
+        raise ValueError(what + f"n_frequencies = {n_freq} != dim_hidden = {hidden} (the first Linear is two "
+                         "hidden x hidden products)")
+    if hidden not in (64, 128):
+        raise ValueError(what + f"dim_hidden = {hidden} (the kernels take 64 / 128)")
+    if dim_in > 4:
+        raise ValueError(what + f"dim_in = {dim_in} (the kernels take 1 .. 4)")
+    dim_out = linears[-1].weight.shape[0]
+    if dim_out != 1:
+        raise ValueError(what + f"dim_out = {dim_out} (the kernels end in one output)")
+    want = [(hidden, 2 * n_freq)] + [(hidden, hidden)] * (len(linears) - 2) + [(1, hidden)]
+    if [tuple(m.weight.shape) for m in linears] != want \
+            or not ops.rff_train_supported(dim_in, hidden, n_freq, len(linears), dim_out):
+        raise ValueError(what + f"unsupported shape: {dim_in} -> {hidden} x {len(linears)} -> {dim_out}")
+    return RffPlan(b, [_Layer(m.weight, m.bias, ops.ACT_RELU, 1.0) for m in linears])
+
+
+def fusable_layers(model, batch_norm: bool = False, modulated: bool = False, rff: bool = False) -> Optional[tuple]:
     """(encoder or None, [_Layer, ...]) if the model is a plain chain of fused layers.  `batch_norm`: also
     accept the reference's BatchNorm decoder blocks of HashMLP (the BatchNorm plan; a BatchNorm decoder the
     kernels do not cover raises ValueError with the reason).  `modulated`: a ModulatedSirenNet gives its
-    ModulatedPlan (both stacks; ValueError with the reason for what csrc/modsiren.hip does not cover)."""
+    ModulatedPlan (both stacks; ValueError with the reason for what csrc/modsiren.hip does not cover).  `rff`: an
+    RffNet gives its RffPlan (ValueError with the reason for what csrc/rff.hip does not cover)."""
     enc, layers = None, []
+    if isinstance(model, models.RffNet):
+        # without the keyword it runs training_step + autograd over the HIP ops
+        return _rff_plan(model) if rff else None
     if isinstance(model, models.ModulatedSirenNet):
         # two interleaved stacks: without the keyword it runs training_step + autograd over the HIP ops
         return _modulated_plan(model) if modulated else None
@@ -184,8 +237,8 @@ class FusedStep:
     """Explicit forward / backward kernel chain over preallocated workspaces."""
 
     def __init__(self, model, optimizer: optim.Adam, world: int = 1, psf_row_budget: int = 1 << 20,
-                 batch_norm: bool = False, modulated: bool = False):
-        plan = fusable_layers(model, batch_norm=batch_norm, modulated=modulated)
+                 batch_norm: bool = False, modulated: bool = False, rff: bool = False):
+        plan = fusable_layers(model, batch_norm=batch_norm, modulated=modulated, rff=rff)
         if plan is None:
             raise ValueError("model is not a fusable chain")
         # BatchNorm plan (csrc/batchnorm.hip): per block linear_fwd -> bn_stats -> bn_act_forward, and
@@ -229,6 +282,11 @@ class FusedStep:
         # zero, so Adam leaves it bit-unchanged.
         self.modulated = self._modulated_plan(plan) if isinstance(plan, ModulatedPlan) else None
         self.use_modulated = self.modulated is not None
+        # RffNet (csrc/rff.hip): the encoding and every Linear in one forward and one backward chain kernel.  Several
+        # ranks ride the flat buffer's one all-reduce, as the modulated plan does; the frozen `encoder.b` is no
+        # parameter of the optimiser and so in no flat buffer.
+        self.rff = self._rff_args(plan) if isinstance(plan, RffPlan) else None
+        self.use_rff = self.rff is not None
         # train_step folds the loss and the head's backward into the forward kernel (needs a
         # sine layer below the last one); forward() + backward() keep the separate kernels
         self.chain_loss = self.use_chain and len(self.layers) >= 3
@@ -429,6 +487,42 @@ class FusedStep:
         with self._phase("mlp_bwd"):
             self._modulated_backward(coords, ws)
 
+    def _rff_args(self, plan: RffPlan):
+        """Arguments of the RFF training kernels: b, the parameters and the flat buffer's gradient views."""
+        ls = plan[1]
+        return dict(b=plan.b.data, weights=[l.weight.data for l in ls], biases=[l.bias.data for l in ls],
+                    n_layers=len(ls), hidden=ls[0].weight.shape[0],
+                    d_weights=[g[0] for g in self._grads], d_biases=[g[1] for g in self._grads])
+
+    def _rff_workspace(self, n: int, train: bool):
+        """Inference: the prediction only (ops.rff_forward keeps its split weights); training: the saved activation
+        and the dz of every hidden Linear, dLoss/dp and the kernels' scratch."""
+        r, dev = self.rff, self.flat.param.device
+        new = lambda *s: torch.empty(*s, device=dev, dtype=torch.float32)  # noqa: E731
+        L, H = r["n_layers"], r["hidden"]
+        ws = dict(y=[new(n, 1)])
+        if train:
+            ws["act"] = [new(n, H) for _ in range(L - 1)]
+            ws["dz"] = [new(n, H) for _ in range(L - 1)]
+            ws["dy"] = new(n, 1)
+            ws["rff_ws"] = ops.rff_train_workspace(n, H, L, dev)
+        return ws
+
+    def _rff_pass(self, coords, target, first, divisor):
+        """forward + loss in one kernel (dLoss/dp leaves with the prediction), then the backward chain."""
+        ws = self._workspace(coords.shape[0], True)
+        r = self.rff
+        with self._phase("zero_grad"):
+            if first:
+                self.flat.grad.zero_()
+            self.loss.zero_()
+        with self._phase("mlp_fwd"):
+            ops.rff_forward_loss(coords, target, r["b"], r["weights"], r["biases"], ws["act"], ws["y"][-1], ws["dy"],
+                                 self.loss, grad_divisor=float(self.world) * float(divisor), ws=ws["rff_ws"])
+        with self._phase("mlp_bwd"):
+            ops.rff_backward(coords, ws["dy"], r["b"], r["weights"], ws["act"], ws["dz"], r["d_weights"],
+                             r["d_biases"], ws=ws["rff_ws"])
+
     def _psf_plan(self, model):
         """PsfSirenNet: S, the offset table and the PSF weights beside the chain plan.  Without the chain
         kernels (e.g. dim_hidden 352) there is no fused PSF step: the model trains through training_step."""
@@ -503,6 +597,10 @@ class FusedStep:
             ws = self._modulated_workspace(n, train)
             self._ws = {k: v for k, v in self._ws.items() if k[1] != train}  # keep one size
             self._ws[key] = ws
+        if ws is None and self.use_rff:
+            ws = self._rff_workspace(n, train)
+            self._ws = {k: v for k, v in self._ws.items() if k[1] != train}  # keep one size
+            self._ws[key] = ws
         if ws is None:
             dev = self.flat.param.device
             new = lambda *s: torch.empty(*s, device=dev, dtype=torch.float32)  # noqa: E731
@@ -541,6 +639,14 @@ class FusedStep:
             with self._phase("mlp_fwd"):
                 ops.modsiren_forward(coords, m["sw"], m["sb"], m["mw"], m["mb"], m["w0_first"], m["w0"],
                                      saved=ws["saved"] if train else None, y=ws["y"][-1], ws=ws["mod_ws"])
+            return ws["y"][-1], ws
+        if self.use_rff:
+            if train:
+                raise RuntimeError("RffNet: the fused step takes its loss inside the forward kernel, train with "
+                                   "train_step")
+            r = self.rff
+            with self._phase("mlp_fwd"):
+                ops.rff_forward(coords, r["b"], r["weights"], r["biases"], y=ws["y"][-1])
             return ws["y"][-1], ws
         if self.encoder is not None and train and self.use_tiny and self._overlap_plan(n):
             # lookup on its own stream, queued BEFORE the decoder (which backward() queues on the
@@ -802,6 +908,8 @@ class FusedStep:
         1 / (world * divisor)."""
         if self.psf is not None:
             raise RuntimeError("PsfSirenNet: its loss is taken through the PSF, train with train_step")
+        if self.use_rff:
+            raise RuntimeError("RffNet: the fused step takes its loss inside the forward kernel, train with train_step")
         div = float(self.world) * float(divisor)
         if self.use_modulated:
             with self._phase("zero_grad"):
@@ -999,6 +1107,9 @@ class FusedStep:
         elif self.use_modulated:
             self._pending = []
             self._modulated_pass(coords, target, first, divisor)
+        elif self.use_rff:
+            self._pending = []
+            self._rff_pass(coords, target, first, divisor)
         elif self.use_chain and self.chain_loss:
             self._pending = []
             self._chain_loss_pass(coords, target, first, divisor)
@@ -1097,6 +1208,8 @@ class SteadyLoop:
             return "the BatchNorm plan runs eagerly (FusedStep.train_step), it has no native form"
         if getattr(step, "use_modulated", False):
             return "ModulatedSirenNet: the modulated plan runs eagerly (FusedStep.train_step), it has no native form"
+        if getattr(step, "use_rff", False):
+            return "RffNet: the RFF plan runs eagerly (FusedStep.train_step), it has no native form"
         if step.world != 1 and (step.dp_mode != "all_reduce" or step.grad_buckets > 1):
             return "several ranks: the plain all-reduce form only (one reduction of the flat gradient)"
         if not (step.use_tiny and step.encoder is not None):
@@ -1339,8 +1452,11 @@ class Trainer:
                  precision: int = 32, log_every: int = 0, distributed: bool = True,
                  accumulate_grad_batches=None, dp_mode: str = "all_reduce", grad_buckets: int = 1,
                  batch_group: int = 1, native_steps: bool = True, fused_batchnorm: bool = False,
-                 fused_modulated: bool = False):
-        """`fused_modulated`: train (and predict) a ModulatedSirenNet through FusedStep's modulated plan
+                 fused_modulated: bool = False, fused_rff: bool = False):
+        """`fused_rff`: train (and predict) an RffNet through FusedStep's RFF plan (csrc/rff.hip) instead of
+        training_step + autograd (opt-in, like `fused_modulated`; a shape the kernels do not cover keeps the
+        autograd path).
+        `fused_modulated`: train (and predict) a ModulatedSirenNet through FusedStep's modulated plan
         (csrc/modsiren.hip) instead of training_step + autograd (opt-in, like `fused_batchnorm`);
         `predict_with_gradient` then asks the model for its fused coordinate gradient (csrc/modsiren_gradient.hip).
         `fused_batchnorm`: train (and predict) the reference's BatchNorm decoder of HashMLP through
@@ -1365,6 +1481,7 @@ class Trainer:
         self.native_steps = bool(native_steps)  # queue steady-state steps with one library call (SteadyLoop)
         self.fused_batchnorm = bool(fused_batchnorm)  # FusedStep's BatchNorm plan for the default HashMLP
         self.fused_modulated = bool(fused_modulated)  # FusedStep's modulated plan for ModulatedSirenNet
+        self.fused_rff = bool(fused_rff)  # FusedStep's RFF plan for RffNet
         self.rank, self.world = 0, 1
         if distributed:
             rank, world, _ = parallel.env_world()
@@ -1389,7 +1506,7 @@ class Trainer:
             model.optimizer = opt
         try:
             self.fused = FusedStep(model, opt, self.world, batch_norm=self.fused_batchnorm,
-                                   modulated=self.fused_modulated)
+                                   modulated=self.fused_modulated, rff=self.fused_rff)
         except ValueError:
             self.fused = None
             opt.flatten()
@@ -1507,7 +1624,7 @@ class Trainer:
             try:
                 fused = FusedStep(model, model.optimizer if hasattr(model, "optimizer")
                                   else model.configure_optimizers(), 1, batch_norm=self.fused_batchnorm,
-                                  modulated=self.fused_modulated)
+                                  modulated=self.fused_modulated, rff=self.fused_rff)
             except ValueError:
                 fused = None
         out = []
