@@ -602,6 +602,30 @@ int64_t mri_rff_forward_workspace_bytes(int32_t hidden, int32_t n_layers);
 int mri_rff_forward(const float* x, int64_t n, int32_t dim_in, int32_t hidden, int32_t n_freq, int32_t n_layers,
                     const float* b, const float* const* weight, const float* const* bias, float* y, void* workspace,
                     int64_t workspace_bytes, void* stream);
+/* Values AND the gradient with respect to the coordinates of the same network (models.py:542-584), y (n) and dydx
+ * (n, dim_in) row-major, dydx[i, d] = d y[i] / d x[i, d], in ONE persistent kernel instead of autograd through the
+ * layer path.  Forward mode: with vp as above, p_l the pre-activation of Linear l and T_l^d = d relu(p_l) / d x_d,
+ *   Tz^d  = [-fl32(2 pi) b[:, d] (.) sin(vp) | fl32(2 pi) b[:, d] (.) cos(vp)]
+ *   T_0^d = [p_0 > 0] (.) (Tz^d W_0^T),   T_l^d = [p_l > 0] (.) (T_{l-1}^d W_l^T),
+ *   dy / dx_d = [p_head > 0] (T_{n_layers-2}^d . w_head)                                 (ReLU'(0) = 0, as torch)
+ * the products of the value rows on more rows, without bias: a point travels as four consecutive rows (value, d/dx_0,
+ * d/dx_1, d/dx_2; dim_in <= 3) or eight (value, d/dx_0 .. d/dx_2 | value, d/dx_3, 0, 0; dim_in = 4) of BOTH LDS images
+ * through the tile loop of mri_rff_forward's kernel, on the same bf16x3 form.  y is mri_rff_forward's bit for bit.
+ * Nothing (n, hidden)-sized is written: the call reads n dim_in floats and writes n (1 + dim_in).  No atomics, a fixed
+ * summation order: bitwise reproducible.  At most 256 workgroups walk tiles of 2048 / hidden points (dim_in = 4: 1024 /
+ * hidden).
+ * mri_rff_gradient_supported (models.py:542-584): exactly what mri_rff_forward_supported accepts.
+ * mri_rff_gradient_workspace_bytes (models.py:542-584): what mri_rff_forward_workspace_bytes reports (the split
+ *   weights; -1 for an unsupported width or depth), 16-byte aligned; its contents on entry do not matter.
+ * mri_rff_gradient (models.py:542-584, autograd of the network with respect to x): every argument is validated before
+ *   any pointer reaches the device (MRI_ERR_INVALID_ARGUMENT, the offending argument named in mri_last_error); n = 0
+ *   returns 0 without a launch.  b / weight / bias as mri_rff_forward; x, y and dydx are accessed 4 bytes at a time
+ *   at any 4-byte aligned address, nothing is written beyond row n. */
+int mri_rff_gradient_supported(int32_t dim_in, int32_t hidden, int32_t n_freq, int32_t n_layers, int32_t dim_out);
+int64_t mri_rff_gradient_workspace_bytes(int32_t hidden, int32_t n_layers);
+int mri_rff_gradient(const float* x, int64_t n, int32_t dim_in, int32_t hidden, int32_t n_freq, int32_t n_layers,
+                     const float* b, const float* const* weight, const float* const* bias, float* y, float* dydx,
+                     void* workspace, int64_t workspace_bytes, void* stream);
 /* ---- RffNet: fused training step (csrc/rff.hip) ---------------------------------------------
  * Forward with the loss and the backward chain of the same network, in place of training_step + autograd over the
  * layer ops (models.py:542-584 RffNet.forward; models.py:61-66 training_step: F.mse_loss).  Notation: Linears

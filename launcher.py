@@ -62,7 +62,8 @@ def parse_args(argv=None):
     p.add_argument("--fused_rff", action="store_true",
                    help="RffNet: train and predict through the fused RFF kernel chain (encoding, every Linear and "
                         "the loss of a row tile in one kernel, one backward chain kernel) instead of training_step + "
-                        "autograd; needs n_frequencies == dim_hidden in {64, 128}, else the autograd path stays")
+                        "autograd; needs n_frequencies == dim_hidden in {64, 128}, else the autograd path stays; with "
+                        "--save_gradient the gradient volumes come from the fused RFF gradient kernel")
     p.add_argument("--no_batchnorm", action="store_true",
                    help="HashMLP without the BatchNorm1d of its decoder blocks, GELU kept (the notebook's decoder, "
                         "Linear -> GELU twice): trains through the one-kernel shallow decoder step")
@@ -88,7 +89,8 @@ def parse_args(argv=None):
                         "change of the network's output per voxel step along each axis (models with one output; "
                         "SirenNet / PsfSirenNet through the fused gradient kernel, a 4-D volume's temporal derivative "
                         "included; ModulatedSirenNet with --fused_modulated through the fused modulated gradient kernel "
-                        "for volumes of up to three axes; the others through autograd), and for every interpolation{shape}.nii.gz a "
+                        "for volumes of up to three axes; RffNet with --fused_rff through the fused RFF gradient kernel, "
+                        "4-D volumes included; the others through autograd), and for every interpolation{shape}.nii.gz a "
                         "gradient_interpolation{shape}.nii.gz of shape + (dim_in,) in voxel steps of THAT grid")
     p.add_argument("--out_dir", type=str, default=None)
     p.add_argument("--max_steps", type=int, default=-1)

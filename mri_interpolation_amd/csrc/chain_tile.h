@@ -1,7 +1,7 @@
-// The device side of the LDS-image tile loop (namespace chain).  Eight persistent kernels walk it: siren_forward_kernel
+// The device side of the LDS-image tile loop (namespace chain).  Nine persistent kernels walk it: siren_forward_kernel
 // and siren_backward_kernel (siren_chain.hip), modsiren_forward_kernel and modsiren_backward_kernel (modsiren.hip),
-// siren_gradient_kernel (siren_gradient.hip), modsiren_gradient_kernel (modsiren_gradient.hip), rff_forward_kernel and
-// rff_backward_kernel (rff.hip).  Their epilogues
+// siren_gradient_kernel (siren_gradient.hip), modsiren_gradient_kernel (modsiren_gradient.hip), rff_forward_kernel,
+// rff_gradient_kernel and rff_backward_kernel (rff.hip).  Their epilogues
 // differ and stay with them; what they decide alike is written here once:
 //
 //   TileShape            the geometry of a tile for a hidden width

@@ -18,6 +18,9 @@
 //                               once per call and streamed from L2 in 16-deep chunks by LDS-DMA (chain_tile.h).  The
 //                               head is a row . w dot product per wave.  Its training form (LOSS) also writes every
 //                               hidden a_l once, dLoss/dp per row and the workgroup's share of the loss.
+//   rff_gradient_kernel         y AND dy/dx, forward mode: the inference walk with four (dim_in <= 3) or eight (dim_in = 4)
+//                               rows per point in both images, the value row and the tangent rows of the axes; a tangent
+//                               passes a ReLU where its value row's pre-activation is positive.
 //   rff_backward_kernel         the same walk from the head down with ONE image, dz_l = da_l (.) [a_l > 0]; dz_l leaves
 //                               once per Linear, da_{l-1} = dz_l W_l against the transposed splits; bias and head
 //                               gradients go to the workgroup's slab (slab.h, RffBwdSlab).
@@ -274,6 +277,195 @@ __global__ __launch_bounds__(kThreads) void rff_forward_kernel(const RffArgs a) 
       float sl = 0.f;
       for (int w = 0; w < 8; ++w) sl += sm.red[w];
       a.partial[blockIdx.x] = sl * a.inv_n;
+    }
+  }
+}
+
+// ------------------------------------------------------------------------- values and coordinate gradient, forward mode
+// y and dy/dx from ONE walk of rff_forward_kernel's inference tile loop.  With u_f = (fl32(2 pi) x) . b_f, z = [cos u |
+// sin u], p_0 = z W_0^T + beta_0, a_l = relu(p_l), p_l = a_{l-1} W_l^T + beta_l, y = relu(p_{L-1}), the tangent
+// T_l^d = d a_l / d x_d:
+//   Tz^d  = [-fl32(2 pi) b[:, d] (.) sin u | fl32(2 pi) b[:, d] (.) cos u]
+//   T_0^d = [p_0 > 0] (.) (Tz^d W_0^T)       T_l^d = [p_l > 0] (.) (T_{l-1}^d W_l^T)       (no bias on tangent rows)
+//   dy / dx_d = [p_{L-1} > 0] (T_{L-2}^d . w_head)                                         (ReLU'(0) = 0, as torch)
+// The tangent rows go through the value row's products as more rows of BOTH images.  dim_in <= 3: a point owns four
+// consecutive rows at a 4-aligned position, [value, d/dx_0, d/dx_1, d/dx_2] (the cos image: the cos halves, the sin
+// image: the sin halves).  dim_in = 4: eight rows in siren_gradient.hip's order [value, d/dx_0, d/dx_1, d/dx_2 | value,
+// d/dx_3, 0, 0], the value row written twice, so that register 4 q of EITHER lane half is a value row and 4 q + 1 ..
+// 4 q + 3 are its tangents (acc_row): the epilogue is lane-local and a tangent register needs only the sign of its
+// value register's pre-activation.  The value rows are rff_forward_kernel's, expression by expression: y is its y
+// bit for bit.  Nothing (n, H)-sized is written: the call reads n dim_in floats and writes n (1 + dim_in).  No atomics,
+// a fixed summation order.
+template <int HH, int SL>
+struct RGradShape : TileShape<HH, 32, SL> {
+  using T = TileShape<HH, 32, SL>;
+  static constexpr int ppt = T::points / T::groups;  // points per thread of the encoding phase: 4 (8 slots: 2)
+  static_assert(HH == 64 || HH == 128, "hidden width");
+  static_assert(SL == 4 || SL == 8, "image rows per point");
+  static_assert(ppt % 2 == 0 && ppt * T::groups == T::points, "encoding-phase mapping");
+  static_assert((T::rows / 8) % SL == 0, "a point's rows belong to one wave of the head");
+};
+
+struct RffGradArgs {
+  const float* x;  // (n, dim_in)
+  int64_t n;
+  int dim_in, L;   // as RffArgs
+  const float* b;  // (H, dim_in)
+  const float* bias[kMaxSine];
+  const float* w_head;
+  float* y;            // (n)
+  float* dydx;         // (n, dim_in)
+  const char* wsplit;  // as RffArgs
+};
+
+template <class S>
+struct RffGradSmem {
+  char wbuf[2][2][S::chunk_bytes] __attribute__((aligned(16)));  // [buffer][matrix: cos / only, sin]
+  float img_c[S::rows * S::ld];  // point p in rows slots p .. : cos u and the cos halves of Tz^d, then every layer's output
+  float img_s[S::rows * S::ld];  //                              sin u and the sin halves of Tz^d
+  float xs[S::points * S::slots] __attribute__((aligned(16)));  // coordinates of the tile's points, padded to slots
+  float bias[kMaxSine][S::H];
+  float w_last[S::H];
+};
+
+template <class S>
+__global__ __launch_bounds__(kThreads) void rff_gradient_kernel(const RffGradArgs a) {
+  __shared__ RffGradSmem<S> sm;
+  constexpr int H = S::H, kSlots = S::slots;
+  const Lanes<S> ln;
+  const int tid = ln.tid, n0 = ln.n0;
+  const int L = a.L, n_mm = L - 1;  // as rff_forward_kernel
+  const int dim_in = a.dim_in;
+
+  for (int l = 0; l < n_mm; ++l) load_vector<H>(sm.bias[l], a.bias[l], tid);
+  load_vector<H>(sm.w_last, a.w_head, tid);
+  const float b_last = a.bias[L - 1][0];
+  // the encoding phase: thread <-> (frequency, group of points); the frequency's row of b stays in registers, and
+  // fl32(2 pi) b[:, d], the factor of axis d's tangent rows (0 for an absent axis: its rows come out as zeros)
+  const int col = tid % H, q0 = (tid / H) * S::ppt;
+  float br[kFwdIn], tb[kFwdIn];
+#pragma unroll
+  for (int d = 0; d < kFwdIn; ++d) {
+    br[d] = d < dim_in ? a.b[col * dim_in + d] : 0.f;
+    tb[d] = kTwoPi * br[d];
+  }
+
+  const int64_t tiles = (a.n + S::points - 1) / S::points;
+  const float* c_row = sm.img_c + ln.fragment_offset();
+  const float* s_row = sm.img_s + ln.fragment_offset();
+  int boff[1];
+  ln.weight_offsets(boff);
+  const int64_t smb = split_matrix_bytes(H);
+
+  ChunkStream<S, 1> stream(n_mm, tiles);
+  auto issue = [&](int layer, int kc, int buf) {
+    if (layer == 1) {
+      issue_chunk<S>(a.wsplit, kc, sm.wbuf[buf][0], ln.wave, ln.lane);
+      issue_chunk<S>(a.wsplit + smb, kc, sm.wbuf[buf][1], ln.wave, ln.lane);
+    } else {
+      issue_chunk<S>(a.wsplit + (int64_t)layer * smb, kc, sm.wbuf[buf][0], ln.wave, ln.lane);
+    }
+  };
+  stream.prime(issue);
+
+  for (int64_t tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
+    const int64_t p0 = tile * S::points;  // first point of the tile
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    __builtin_amdgcn_s_barrier();  // previous tile is done with the images / xs
+    stage_coords<kSlots>(sm.xs, a.x, p0, S::points, a.n, dim_in, tid);
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    __builtin_amdgcn_s_barrier();
+    // ---- the encoding on the VALU: all rows of a point in both images ------------------------------------------------
+#pragma unroll 1
+    for (int i = 0; i < S::ppt; i += 2) {
+      const float4 xa = *reinterpret_cast<const float4*>(sm.xs + (q0 + i) * kSlots);
+      const float4 xb = *reinterpret_cast<const float4*>(sm.xs + (q0 + i + 1) * kSlots);
+      const float u0 = rff_phase(xa, br), u1 = rff_phase(xb, br);
+      float s0, c0, s1, c1;
+      sincos_fast2(u0, u1, &s0, &c0, &s1, &c1);
+      const bool live0 = p0 + q0 + i < a.n, live1 = p0 + q0 + i + 1 < a.n;
+      float* rc0 = sm.img_c + (q0 + i) * kSlots * S::ld + col;
+      float* rc1 = rc0 + kSlots * S::ld;
+      float* rs0 = sm.img_s + (q0 + i) * kSlots * S::ld + col;
+      float* rs1 = rs0 + kSlots * S::ld;
+      rc0[0] = live0 ? c0 : 0.f, rc1[0] = live1 ? c1 : 0.f;
+      rs0[0] = live0 ? s0 : 0.f, rs1[0] = live1 ? s1 : 0.f;
+#pragma unroll
+      for (int d = 0; d < 3; ++d) {
+        rc0[(1 + d) * S::ld] = live0 ? -(tb[d] * s0) : 0.f;
+        rc1[(1 + d) * S::ld] = live1 ? -(tb[d] * s1) : 0.f;
+        rs0[(1 + d) * S::ld] = live0 ? tb[d] * c0 : 0.f;
+        rs1[(1 + d) * S::ld] = live1 ? tb[d] * c1 : 0.f;
+      }
+      if constexpr (kSlots == 8) {  // upper lane half of the accumulator: the value row again, d/dx_3, two zero rows
+        rc0[4 * S::ld] = live0 ? c0 : 0.f, rc1[4 * S::ld] = live1 ? c1 : 0.f;
+        rs0[4 * S::ld] = live0 ? s0 : 0.f, rs1[4 * S::ld] = live1 ? s1 : 0.f;
+        rc0[5 * S::ld] = live0 ? -(tb[3] * s0) : 0.f, rc1[5 * S::ld] = live1 ? -(tb[3] * s1) : 0.f;
+        rs0[5 * S::ld] = live0 ? tb[3] * c0 : 0.f, rs1[5 * S::ld] = live1 ? tb[3] * c1 : 0.f;
+        rc0[6 * S::ld] = rc0[7 * S::ld] = 0.f, rc1[6 * S::ld] = rc1[7 * S::ld] = 0.f;
+        rs0[6 * S::ld] = rs0[7 * S::ld] = 0.f, rs1[6 * S::ld] = rs1[7 * S::ld] = 0.f;
+      }
+    }
+    // ---- the H x H layers, back into the cos image ---------------------------------------------------------------------
+    auto layer = [&](int l, auto dual) {
+      constexpr bool DUAL = decltype(dual)::value;  // the first Linear: cos and sin halves into one accumulator
+      f32x16 acc[1];
+#pragma unroll
+      for (int r = 0; r < 16; ++r) acc[0][r] = 0.f;
+      x3::Frag fc, fs;
+#pragma unroll
+      for (int kc = 0; kc < S::chunks; ++kc, stream.consumed()) {
+        stream.advance(tile, l, kc, issue);
+        if (kc == 0) {
+          fc = first_fragment(c_row);
+          if (DUAL) fs = first_fragment(s_row);
+        }
+        mma_step<S>(acc, fc, c_row, kc, sm.wbuf[stream.buffer()][0], boff);
+        if (DUAL) mma_step<S>(acc, fs, s_row, kc, sm.wbuf[stream.buffer()][1], boff);
+      }
+      // epilogue: registers 4 q .. 4 q + 3 are one point's value and tangent rows (8 slots: of either half of the
+      // point, the value row being there twice); the tangents pass where the value's pre-activation is positive
+      const float bj = sm.bias[l - 1][n0];
+      float v[16];
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        const float p = acc[0][4 * q] + bj;
+        v[4 * q] = relu_f(p);
+#pragma unroll
+        for (int j = 1; j < 4; ++j) v[4 * q + j] = p > 0.f ? acc[0][4 * q + j] : 0.f;
+      }
+      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+      __builtin_amdgcn_s_barrier();  // every wave has read the images for the last time
+      store_acc<S>(sm.img_c, ln, v);
+    };
+    layer(1, std::true_type{});
+    for (int l = 2; l <= n_mm; ++l) layer(l, std::false_type{});
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    __builtin_amdgcn_s_barrier();  // the image is complete
+    // ---- head: image row . w_head, one wave per row and a point's rows in ONE wave, the value row first: slot 0 ->
+    //      y = relu(. + b_head), slot 1 + d -> dydx[:, d] where the value's pre-activation is positive; of the upper four
+    //      of 8 slots only slot 5 -> dydx[:, 3] is stored ----------------------------------------------------------------
+    {
+      const HeadDot<S> head(sm.w_last, ln.lane);
+      bool pos = false;  // (lane 0's: of the point whose rows the wave is walking)
+#pragma unroll 4
+      for (int i = 0; i < S::rows / 8; ++i) {
+        const int row = ln.wave * (S::rows / 8) + i;  // wave-uniform
+        const int slot = row % kSlots;
+        const int64_t p = p0 + row / kSlots;
+        const int axis = slot < 4 ? slot - 1 : (slot == 5 ? 3 : kFwdIn);  // wave-uniform; -1: the value
+        if (axis >= dim_in || p >= a.n) continue;
+        const float acc1 = head(sm.img_c + row * S::ld);
+        if (ln.lane == 0) {
+          if (slot == 0) {
+            const float pre = acc1 + b_last;
+            pos = pre > 0.f;
+            a.y[p] = relu_f(pre);
+          } else {
+            a.dydx[p * dim_in + axis] = pos ? acc1 : 0.f;
+          }
+        }
+      }
     }
   }
 }
@@ -621,6 +813,19 @@ template <class S>
 int rff_blocks(int64_t n) { return (int)std::min<int64_t>(ceil_div(n, S::rows), 256); }  // one workgroup per CU
 // the two halves of the first Linear and the n_layers - 2 square ones
 int64_t rff_split_bytes(int hidden, int n_layers) { return (int64_t)n_layers * split_matrix_bytes(hidden); }
+// ... into `out`: Linear 0 is (H, 2F), its cos half starts at column 0, its sin half at column F, both with row stride 2F
+int split_forward_weights(const float* const* weight, int hidden, int n_freq, int n_layers, char* out, hipStream_t st) {
+  const int64_t smb = split_matrix_bytes(hidden);
+  const float* const halves[2] = {weight[0], weight[0] + n_freq};
+  if (int rc = split_weights_ld(halves, 2, hidden, 2 * n_freq, false, out, smb, st)) return rc;
+  return split_weights_ld(weight + 1, n_layers - 2, hidden, hidden, false, out + 2 * smb, smb, st);
+}
+template <class S>
+int launch_rff_gradient(const RffGradArgs& a, hipStream_t st) {
+  const int blocks = (int)std::min<int64_t>(ceil_div(a.n, S::points), 256);  // one workgroup per CU
+  hipLaunchKernelGGL((rff_gradient_kernel<S>), dim3(blocks), dim3(kThreads), 0, st, a);
+  return check_launch("rff_gradient_kernel");
+}
 
 int check_encode(const float* x, int64_t n, int dim_in, const float* b, int n_freq) {
   MRI_REQUIRE(dim_in >= 1 && dim_in <= kEncIn, "RFF encoding: dim_in = %d is not supported (1 .. %d)", dim_in, kEncIn);
@@ -712,16 +917,60 @@ extern "C" int mri_rff_forward(const float* x, int64_t n, int32_t dim_in, int32_
   a.w_head = weight[n_layers - 1];
   a.wsplit = static_cast<const char*>(workspace);
   hipStream_t st = (hipStream_t)stream;
-  char* const out = static_cast<char*>(workspace);
-  const int64_t smb = split_matrix_bytes(hidden);
-  // Linear 0 is (H, 2F): its cos half starts at column 0, its sin half at column F, both with row stride 2F
-  const float* const halves[2] = {weight[0], weight[0] + n_freq};
-  if (int rc = split_weights_ld(halves, 2, hidden, 2 * n_freq, false, out, smb, st)) return rc;
-  if (int rc = split_weights_ld(weight + 1, n_layers - 2, hidden, hidden, false, out + 2 * smb, smb, st)) return rc;
+  if (int rc = split_forward_weights(weight, hidden, n_freq, n_layers, static_cast<char*>(workspace), st)) return rc;
   return dispatch_hidden_mod(hidden, [&](auto h) {
     using S = RShape<decltype(h)::value>;
     hipLaunchKernelGGL((rff_forward_kernel<false, S>), dim3(rff_blocks<S>(n)), dim3(kThreads), 0, st, a);
     return check_launch("rff_forward_kernel");
+  });
+}
+
+extern "C" int mri_rff_gradient_supported(int32_t dim_in, int32_t hidden, int32_t n_freq, int32_t n_layers,
+                                          int32_t dim_out) {
+  return rff_supported(dim_in, hidden, n_freq, n_layers, dim_out) ? 1 : 0;
+}
+
+extern "C" int64_t mri_rff_gradient_workspace_bytes(int32_t hidden, int32_t n_layers) {
+  if (!rff_supported(1, hidden, hidden, n_layers, 1)) return -1;
+  return rff_split_bytes(hidden, n_layers);
+}
+
+extern "C" int mri_rff_gradient(const float* x, int64_t n, int32_t dim_in, int32_t hidden, int32_t n_freq,
+                                int32_t n_layers, const float* b, const float* const* weight,
+                                const float* const* bias, float* y, float* dydx, void* workspace,
+                                int64_t workspace_bytes, void* stream) {
+  MRI_REQUIRE(hidden == 64 || hidden == 128, "fused RFF gradient: hidden = %d is not supported (64 / 128)", hidden);
+  MRI_REQUIRE(n_freq == hidden, "fused RFF gradient: n_freq = %d is not supported (n_freq == hidden = %d)", n_freq,
+              hidden);
+  MRI_REQUIRE(dim_in >= 1 && dim_in <= kFwdIn, "fused RFF gradient: dim_in = %d is not supported (1 .. %d)", dim_in,
+              kFwdIn);
+  MRI_REQUIRE(n_layers >= 2 && n_layers <= kMaxSine, "fused RFF gradient: n_layers = %d is not supported (2 .. %d)",
+              n_layers, kMaxSine);
+  if (int rc = check_gradient_io(x, n, y, dydx)) return rc;
+  if (n == 0) return MRI_OK;
+  MRI_REQUIRE(b, "b is NULL");
+  MRI_REQUIRE(weight, "weight is NULL");
+  MRI_REQUIRE(bias, "bias is NULL");
+  MRI_REQUIRE(aligned_to(b, 4), "b must be 4-byte aligned");
+  const int64_t need = rff_split_bytes(hidden, n_layers);
+  MRI_REQUIRE(workspace && workspace_bytes >= need && aligned_to(workspace, 16),
+              "workspace: the fused RFF gradient needs %lld bytes, 16-byte aligned (mri_rff_gradient_workspace_bytes)",
+              (long long)need);
+  RffGradArgs a{};
+  a.x = x, a.n = n, a.dim_in = dim_in, a.L = n_layers, a.b = b, a.y = y, a.dydx = dydx;
+  for (int l = 0; l < n_layers; ++l) {
+    MRI_REQUIRE(weight[l], "weight[%d] is NULL", l);
+    MRI_REQUIRE(bias[l], "bias[%d] is NULL", l);
+    MRI_REQUIRE(aligned_to(weight[l], 4) && aligned_to(bias[l], 4), "weight[%d] / bias[%d] must be 4-byte aligned", l, l);
+    a.bias[l] = bias[l];
+  }
+  a.w_head = weight[n_layers - 1];
+  a.wsplit = static_cast<const char*>(workspace);
+  hipStream_t st = (hipStream_t)stream;
+  if (int rc = split_forward_weights(weight, hidden, n_freq, n_layers, static_cast<char*>(workspace), st)) return rc;
+  return dispatch_hidden_mod(hidden, [&](auto h) {
+    return dim_in <= 3 ? launch_rff_gradient<RGradShape<decltype(h)::value, 4>>(a, st)
+                       : launch_rff_gradient<RGradShape<decltype(h)::value, 8>>(a, st);
   });
 }
 
@@ -820,10 +1069,7 @@ extern "C" int mri_rff_forward_loss(const float* x, const float* target, int64_t
   a.grad_scale = (float)(2.0 / ((double)n_total * (double)grad_divisor));
   a.inv_n = (float)(1.0 / (double)n_total);
   hipStream_t st = (hipStream_t)stream;
-  const int64_t smb = split_matrix_bytes(hidden);
-  const float* const halves[2] = {weight[0], weight[0] + n_freq};
-  if (int rc = split_weights_ld(halves, 2, hidden, 2 * n_freq, false, wsplit, smb, st)) return rc;
-  if (int rc = split_weights_ld(weight + 1, n_layers - 2, hidden, hidden, false, wsplit + 2 * smb, smb, st)) return rc;
+  if (int rc = split_forward_weights(weight, hidden, n_freq, n_layers, wsplit, st)) return rc;
   const int blocks = rff_blocks_of(hidden, n);
   if (int rc = dispatch_hidden_mod(hidden, [&](auto h) {
         using S = RShape<decltype(h)::value>;

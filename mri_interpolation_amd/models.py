@@ -472,7 +472,8 @@ class RffNet(BaseMLP):
     `forward` is the encoding op and the layer ops (differentiable: training_step + autograd, and
     forward_with_gradient through the encoder's input gradient).  Inference -- `predict_step`, and `forward` under
     torch.no_grad() in eval mode -- runs ONE kernel (ops.rff_forward, csrc/rff.hip) where `_inference_plan` finds it
-    serves; `fused_inference=False` keeps inference on the layer path."""
+    serves; `fused_inference=False` keeps inference on the layer path.  `forward_with_gradient(x, fused=True)` takes
+    the fused coordinate-gradient kernel (ops.rff_gradient) under the same plan."""
 
     def __init__(self, dim_in: int, dim_hidden: int = 128, dim_out: int = 1, n_layers: int = 8,
                  n_frequencies: int = 128, sigma: float = 10.0, activation=nn.ReLU, lr: float = 1e-4,
@@ -522,6 +523,20 @@ class RffNet(BaseMLP):
             return None
         return dict(b=b.detach(), weights=[m.weight.detach() for m in linears],
                     biases=[m.bias.detach() for m in linears])
+
+    def forward_with_gradient(self, x, fused: bool = False) -> Tuple[torch.Tensor, torch.Tensor]:
+        """The generic body (autograd through the layer path and the encoder's input gradient).  `fused` (opt-in, what
+        Trainer(fused_rff=True) passes): ONE kernel that carries the value and the tangents of a point through the
+        Linears together (ops.rff_gradient) where `_inference_plan` finds the fused kernels serve -- the gradient
+        kernel takes exactly the inference kernel's shapes --; everything else stays the generic body."""
+        if fused:
+            if self.dim_out != 1:
+                raise ValueError(f"forward_with_gradient needs dim_out == 1 (got {self.dim_out})")
+            plan = self._inference_plan(x)
+            if plan is not None:
+                with torch.no_grad():
+                    return ops.rff_gradient(x.detach(), **plan)
+        return BaseMLP.forward_with_gradient(self, x)
 
     def configure_optimizers(self):
         # torch.optim.Adam skips encoder.b (it never has a gradient); the flat buffers never take it

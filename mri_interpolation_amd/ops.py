@@ -485,42 +485,77 @@ def rff_forward_supported(dim_in: int, hidden: int, n_frequencies: int, n_layers
 _rff_ws = {}
 
 
+def _rff_check(what, x, b, weights, biases, outputs):
+    """(n, dim_in, hidden, n_layers) of an inference call.  The library sees pointers only: a mismatched shape would be
+    read out of bounds on the device."""
+    n, dim_in = x.shape
+    n_layers, hidden = len(weights), weights[0].shape[0]
+    if len(biases) != n_layers or n_layers < 2:
+        raise ValueError(f"{what}: at least two Linears, one bias per weight")
+    if b.dim() != 2 or b.shape[1] != dim_in:
+        raise ValueError(f"{what}: b is (n_frequencies, dim_in = {dim_in}), got {tuple(b.shape)}")
+    want = [(hidden, 2 * b.shape[0])] + [(hidden, hidden)] * (n_layers - 2) + [(1, hidden)]
+    for i, (w, v, shape) in enumerate(zip(weights, biases, want)):
+        if tuple(w.shape) != shape or tuple(v.shape) != (shape[0],):
+            raise ValueError(f"{what}: Linear {i} is {shape} with a bias of {shape[0]}, got {tuple(w.shape)} and "
+                             f"{tuple(v.shape)}")
+    for t in [b] + list(outputs) + list(weights) + list(biases):
+        if not t.is_contiguous() or t.dtype != torch.float32:
+            raise ValueError(f"{what} needs contiguous float32 parameters and buffers")
+    return n, dim_in, hidden, n_layers
+
+
+def _rff_scratch(device, need):
+    """The inference calls' workspace (the split weights), one per device, grown on demand."""
+    ws = _rff_ws.get(device.index)
+    if need > 0 and (ws is None or ws.numel() * 4 < need):
+        if ws is not None:
+            torch.cuda.synchronize(device)
+        ws = torch.empty((need + 3) // 4, dtype=torch.float32, device=device)
+        _rff_ws[device.index] = ws
+    if ws is None:  # (the library refuses the shape with its reason)
+        ws = torch.empty(64, dtype=torch.float32, device=device)
+    return ws
+
+
 def rff_forward(x, b, weights, biases, y=None):
     """y (n, 1) = RffNet(x), ReLU behind every Linear, in one persistent kernel (csrc/rff.hip): the encoding lives in
     two LDS images, nothing (n, hidden)-sized is written.  weights / biases: the decoder's Linears, the head last."""
     _gpu(x, b, y, *weights, *biases)
     x = _rowmajor(x).contiguous()
-    n, dim_in = x.shape
-    n_layers, hidden = len(weights), weights[0].shape[0]
-    if len(biases) != n_layers or n_layers < 2:
-        raise ValueError("rff_forward: at least two Linears, one bias per weight")
-    # the library sees pointers only: a mismatched shape would be read out of bounds on the device
-    if b.dim() != 2 or b.shape[1] != dim_in:
-        raise ValueError(f"rff_forward: b is (n_frequencies, dim_in = {dim_in}), got {tuple(b.shape)}")
-    want = [(hidden, 2 * b.shape[0])] + [(hidden, hidden)] * (n_layers - 2) + [(1, hidden)]
-    for i, (w, v, shape) in enumerate(zip(weights, biases, want)):
-        if tuple(w.shape) != shape or tuple(v.shape) != (shape[0],):
-            raise ValueError(f"rff_forward: Linear {i} is {shape} with a bias of {shape[0]}, got {tuple(w.shape)} and "
-                             f"{tuple(v.shape)}")
     if y is None:
-        y = torch.empty((n, 1), device=x.device, dtype=torch.float32)
-    if y.numel() != n:
+        y = torch.empty((x.shape[0], 1), device=x.device, dtype=torch.float32)
+    if y.numel() != x.shape[0]:
         raise ValueError("rff_forward: y holds n values")
-    for t in [b, y] + list(weights) + list(biases):
-        if not t.is_contiguous() or t.dtype != torch.float32:
-            raise ValueError("rff_forward needs contiguous float32 parameters and buffers")
-    need = _lib.load().mri_rff_forward_workspace_bytes(hidden, n_layers)
-    ws = _rff_ws.get(x.device.index)
-    if need > 0 and (ws is None or ws.numel() * 4 < need):
-        if ws is not None:
-            torch.cuda.synchronize(x.device)
-        ws = torch.empty((need + 3) // 4, dtype=torch.float32, device=x.device)
-        _rff_ws[x.device.index] = ws
-    if ws is None:  # (the library refuses the shape with its reason)
-        ws = torch.empty(64, dtype=torch.float32, device=x.device)
+    n, dim_in, hidden, n_layers = _rff_check("rff_forward", x, b, weights, biases, [y])
+    ws = _rff_scratch(x.device, _lib.load().mri_rff_forward_workspace_bytes(hidden, n_layers))
     _lib.call("mri_rff_forward", _ptr(x), n, dim_in, hidden, b.shape[0], n_layers, _ptr(b), _ptr_array(weights),
               _ptr_array(biases), _ptr(y), _ptr(ws), ws.numel() * 4, _stream())
     return y
+
+
+def rff_gradient_supported(dim_in: int, hidden: int, n_frequencies: int, n_layers: int, dim_out: int) -> bool:
+    return bool(_lib.load().mri_rff_gradient_supported(dim_in, hidden, n_frequencies, n_layers, dim_out))
+
+
+def rff_gradient(x, b, weights, biases, y=None, dydx=None):
+    """(y (n, 1), dydx (n, dim_in)) = RffNet(x) and its gradient with respect to x, dydx[i, d] = dy[i] / dx[i, d], in one
+    persistent kernel (csrc/rff.hip): the value and the tangents of a point travel the Linears together, four rows per
+    point in each of the two LDS images (eight for dim_in = 4); nothing (n, hidden)-sized is written.  y is
+    rff_forward's bit for bit.  Parameters as rff_forward."""
+    _gpu(x, b, y, dydx, *weights, *biases)
+    x = _rowmajor(x).contiguous()
+    if y is None:
+        y = torch.empty((x.shape[0], 1), device=x.device, dtype=torch.float32)
+    if dydx is None:
+        dydx = torch.empty(tuple(x.shape), device=x.device, dtype=torch.float32)
+    if y.numel() != x.shape[0] or dydx.shape != x.shape:
+        raise ValueError("rff_gradient: y holds n values, dydx is (n, dim_in)")
+    n, dim_in, hidden, n_layers = _rff_check("rff_gradient", x, b, weights, biases, [y, dydx])
+    ws = _rff_scratch(x.device, _lib.load().mri_rff_gradient_workspace_bytes(hidden, n_layers))
+    _lib.call("mri_rff_gradient", _ptr(x), n, dim_in, hidden, b.shape[0], n_layers, _ptr(b), _ptr_array(weights),
+              _ptr_array(biases), _ptr(y), _ptr(dydx), _ptr(ws), ws.numel() * 4, _stream())
+    return y, dydx
 
 
 def rff_train_supported(dim_in: int, hidden: int, n_frequencies: int, n_layers: int, dim_out: int) -> bool:

@@ -1640,11 +1640,14 @@ class Trainer:
         """(per-batch predictions (n, 1), per-batch gradients (n, dim_in) with respect to the coordinates): the
         twin of `predict` through `model.forward_with_gradient` (SirenNet / PsfSirenNet: one fused kernel per
         batch; a ModulatedSirenNet under `fused_modulated=True`: its own fused kernel, csrc/modsiren_gradient.hip,
-        where the shape is covered; every other model: autograd through its forward)."""
+        where the shape is covered; an RffNet under `fused_rff=True`: rff_gradient_kernel, csrc/rff.hip, likewise;
+        every other model: autograd through its forward)."""
         if next(model.parameters()).device.type != "cuda":
             model.cuda()
         model.eval()
-        kwargs = dict(fused=True) if self.fused_modulated and isinstance(model, models.ModulatedSirenNet) else {}
+        fused = (self.fused_modulated and isinstance(model, models.ModulatedSirenNet)) \
+            or (self.fused_rff and isinstance(model, models.RffNet))
+        kwargs = dict(fused=True) if fused else {}
         ys, grads = [], []
         for x, _ in dataloaders:
             y, g = model.forward_with_gradient(x, **kwargs)
