@@ -667,6 +667,47 @@ int mri_rff_backward(const float* x, const float* dy, int64_t n, int32_t dim_in,
                      float* const* dz, float* const* d_weight, float* const* d_bias, void* workspace,
                      int64_t workspace_bytes, void* stream);
 
+/* ---- GaborNet: real Gabor (WIRE) layers (csrc/gabor.hip) -----------------------------------
+ * (reference models.py:757-788 RealGaborLayer, models.py:836-885 GaborNet.)  A layer holds two Linears on the same
+ * input, `freqs` and `scale`, and computes omega = w0 * freqs(a), scale = scale(a) * c, cos(omega) * exp(-(scale ** 2))
+ * (models.py:785-788); the network is n_layers such layers dim_in -> hidden -> ... -> hidden -> dim_out, the LAST one
+ * included.  The cosine is correct for every finite argument (the Cody-Waite fast path up to |omega| = 8192, the
+ * library's full-range sincosf beyond); the envelope forms t = fl(fl(c s)^2) in the reference's order and is within
+ * 2 ulp of exp(-t) of that float32 t while the result is a normal float (below: within 2^-126, flushing allowed); s =
+ * +-inf gives 0, NaN gives NaN, as torch.  Every buffer is contiguous row-major and accessed 4 bytes at a time at any
+ * 4-byte aligned address; nothing is written beyond element n hidden; n = 0 returns 0 without a launch.
+ * mri_gabor_activation (models.py:785-788, behind the two Linears): out (n, hidden) = cos(w0 u) exp(-(c s)^2)
+ *   elementwise over u, s (n, hidden).  hidden >= 1, n hidden < 2^38, w0 and c finite.
+ * mri_gabor_activation_backward (models.py:785-788, autograd): with omega = w0 u, sigma = c s, e = exp(-sigma^2),
+ *   du = -g w0 sin(omega) e and ds = -2 c sigma cos(omega) e g; g, du, ds (n, hidden).  du and ds are OVERWRITTEN. */
+int mri_gabor_activation(const float* u, const float* s, int64_t n, int32_t hidden, float w0, float c, float* out,
+                         void* stream);
+int mri_gabor_activation_backward(const float* u, const float* s, const float* g, int64_t n, int32_t hidden, float w0,
+                                  float c, float* du, float* ds, void* stream);
+/* Inference of the whole network (models.py:836-885 GaborNet.forward; models.py:784-788 per layer) in ONE persistent
+ * kernel: layer 0 (dim_in -> hidden, both Linears) runs on the VALU into an f32 LDS image of the row tile; layers
+ * 1 .. n_layers - 2 are two hidden x hidden products each from the SAME image into two accumulators on the bf16 matrix
+ * pipe with three-term operands (f32-accurate), their weights streamed as a pair of chunks; the epilogue
+ * cos(w0 (acc_f + b_f)) exp(-(c (acc_s + b_s))^2) writes the image back; the head is a Gabor layer too, two dot products
+ * per row plus biases: y (n) lies in (-1, 1].  Nothing (n, hidden)-sized is written.  512 threads, at most 256
+ * workgroups, tiles of 128 rows at hidden 128 and 256 rows at hidden 64.  No atomics, a fixed summation order: two
+ * calls agree bitwise.
+ * mri_gabor_forward_supported (models.py:836-864) is the truth about what is served: hidden 64 / 128,
+ *   1 <= dim_in <= 4, 2 <= n_layers <= 8, dim_out 1, a bias on every Linear; anything else is refused.
+ * mri_gabor_forward_workspace_bytes (models.py:860-864): 2 (n_layers - 2) hidden x hidden matrices in three bf16 terms,
+ *   12 (n_layers - 2) hidden^2 bytes (0 for n_layers = 2: workspace may then be NULL); -1 for an unsupported width or
+ *   depth.  The size is exact, 16-byte aligned; its contents on entry do not matter.
+ * mri_gabor_forward (models.py:866-867, 882-885): every argument is validated before any pointer reaches the device
+ *   (MRI_ERR_INVALID_ARGUMENT, the offending argument named in mri_last_error).  freq_weight / freq_bias / scale_weight /
+ *   scale_bias: HOST arrays of n_layers device pointers ([0] (hidden, dim_in), [1 .. n_layers-2] (hidden, hidden),
+ *   [n_layers-1] (1, hidden); biases (hidden), the last (1)).  w0 and c finite. */
+int mri_gabor_forward_supported(int32_t dim_in, int32_t hidden, int32_t n_layers, int32_t dim_out);
+int64_t mri_gabor_forward_workspace_bytes(int32_t hidden, int32_t n_layers);
+int mri_gabor_forward(const float* x, int64_t n, int32_t dim_in, int32_t hidden, int32_t n_layers,
+                      const float* const* freq_weight, const float* const* freq_bias,
+                      const float* const* scale_weight, const float* const* scale_bias, float w0, float c, float* y,
+                      void* workspace, int64_t workspace_bytes, void* stream);
+
 /* ---- PsfSirenNet: the acquisition point-spread function -----------------------------------
  * (reference models.py:397-539.)  A target voxel b is the network averaged over S sample points around it:
  * rows b*S + k of the expanded batch hold x[b] + offsets[k], and the voxel value is sum_k w_k z[b*S + k]

@@ -48,7 +48,11 @@ def parse_args(argv=None):
                         "select MultiResHashGridV2, as in reference models.py:691-708)")
     p.add_argument("--finest_resolution", type=str, help="as --base_resolution (floats allowed)")
     p.add_argument("--n_frequencies", type=int, help="RffNet: Gaussian Fourier frequencies (features: twice as many)")
-    p.add_argument("--sigma", type=float, help="RffNet: standard deviation of the frozen Gaussian projection")
+    p.add_argument("--sigma", type=float,
+                   help="RffNet: standard deviation of the frozen Gaussian projection; GaborNet: the scale c of every "
+                        "layer's Gaussian envelope (the frequency is the config's w0)")
+    p.add_argument("--w0", type=float, help="the config's w0: the frequency factor of SIREN layers behind the first and of "
+                                            "every GaborNet layer")
     p.add_argument("--tiny_mlp", action="store_true",
                    help="HashMLP with the fused ReLU tiny-MLP decoder of hash_config.json")
     p.add_argument("--fused_batchnorm", action="store_true",
@@ -164,6 +168,8 @@ def build_model(config, models):
         everything["final_activation"] = config.final_activation_on
     if config.model_class == "RffNet":
         everything.update(n_frequencies=config.n_frequencies, sigma=config.sigma)
+    if config.model_class == "GaborNet":  # real Gabor layers (the class's default layer_cls), c = sigma
+        everything.update(sigma=config.sigma)
     if config.model_class == "PsfSirenNet":
         spacing = getattr(config, "coordinates_spacing", None)
         if spacing is None:

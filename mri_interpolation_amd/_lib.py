@@ -123,6 +123,9 @@ SIGNATURES = {
     "mri_rff_forward_loss": [_P, _P, _I64, _I64, _I32, _I32, _I32, _I32, _P, C.POINTER(_P), C.POINTER(_P), _F,
                              C.POINTER(_P), _P, _P, _P, _P, _I64, _P],
     "mri_rff_backward": [_P, _P, _I64, _I32, _I32, _I32, _I32, _P] + [C.POINTER(_P)] * 5 + [_P, _I64, _P],
+    "mri_gabor_activation": [_P, _P, _I64, _I32, _F, _F, _P, _P],
+    "mri_gabor_activation_backward": [_P, _P, _P, _I64, _I32, _F, _F, _P, _P, _P],
+    "mri_gabor_forward": [_P, _I64, _I32, _I32, _I32] + [C.POINTER(_P)] * 4 + [_F, _F, _P, _P, _I64, _P],
     "mri_psf_expand": [_P, _I64, _I32, _P, _I32, _P, _P],
     "mri_psf_reduce": [_P, _I64, _I32, _I32, _P, _P, _P],
     "mri_psf_broadcast": [_P, _I64, _I32, _P, _F, _P, _P],
@@ -154,6 +157,7 @@ INT64_GETTERS = {"mri_hashgrid_backward_workspace_bytes": [C.POINTER(GridDesc), 
                  "mri_rff_forward_workspace_bytes": [_I32, _I32],
                  "mri_rff_gradient_workspace_bytes": [_I32, _I32],
                  "mri_rff_backward_workspace_bytes": [_I64, _I32, _I32],
+                 "mri_gabor_forward_workspace_bytes": [_I32, _I32],
                  "mri_hashgrid_forward_signal_blocks": [C.POINTER(GridDesc), _I64],
                  "mri_tiny_mlp_round_rows": [_I32, _I32, _I64]}
 INT_GETTERS = {"mri_tiny_mlp_supported": [_I32, _I32, _I32],
@@ -166,7 +170,8 @@ INT_GETTERS = {"mri_tiny_mlp_supported": [_I32, _I32, _I32],
                "mri_modsiren_gradient_supported": [_I32, _I32, _I32, _I32],
                "mri_rff_forward_supported": [_I32, _I32, _I32, _I32, _I32],
                "mri_rff_gradient_supported": [_I32, _I32, _I32, _I32, _I32],
-               "mri_rff_train_supported": [_I32, _I32, _I32, _I32, _I32]}  # return a plain value, not a status
+               "mri_rff_train_supported": [_I32, _I32, _I32, _I32, _I32],
+               "mri_gabor_forward_supported": [_I32, _I32, _I32, _I32]}  # return a plain value, not a status
 
 _lib = None
 

@@ -19,7 +19,7 @@ OBJ = os.path.join(PKG, "build")
 LIB = os.path.join(PKG, "libmri_inr.so")
 SOURCES = ["hashgrid.hip", "hashgrid_bwd.hip", "linear.hip", "linear_small.hip", "mlp_fused.hip", "mlp_x3.hip", "mlp_shallow.hip", "train_ops.hip",
            "frequency.hip", "siren_chain.hip", "siren_rows.hip", "siren_gradient.hip", "modsiren.hip", "modsiren_gradient.hip", "fused_step.hip", "psf.hip", "batchnorm.hip",
-           "rff.hip"]
+           "rff.hip", "gabor.hip"]
 FLAGS = ["-O3", "--offload-arch=gfx950", "-std=c++17", "-fPIC",
          # the reference multiplies and adds separately (encoding.py:111-128, torch Adam);
          # keep those roundings instead of contracting to fma
@@ -33,7 +33,7 @@ FLAGS = ["-O3", "--offload-arch=gfx950", "-std=c++17", "-fPIC",
 # The decoder kernels measured the same either way.
 EXTRA_FLAGS = {"siren_chain.hip": ["-fno-slp-vectorize"], "modsiren.hip": ["-fno-slp-vectorize"],
                "siren_gradient.hip": ["-fno-slp-vectorize"], "modsiren_gradient.hip": ["-fno-slp-vectorize"],
-               "rff.hip": ["-fno-slp-vectorize"],
+               "rff.hip": ["-fno-slp-vectorize"], "gabor.hip": ["-fno-slp-vectorize"],
                "siren_rows.hip": ["-fno-slp-vectorize",
                                                                                      # the order fixed before register allocation (sched_group_barrier)
                                                                                      # is the one wanted: the post-RA scheduler re-solves the groups with

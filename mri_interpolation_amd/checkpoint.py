@@ -53,6 +53,7 @@ def reference_state_dict(model) -> "OrderedDict[str, torch.Tensor]":
     if type(model).__name__ in ("HashMLP", "RffNet"):  # (RffNet's frozen `encoder.b` is a parameter there too: Adam
         # numbers it and never holds state for it)
         sd = OrderedDict(list(_dead_base_stack(model).items()) + list(sd.items()))
+    # (GaborNet derives from LightningModule directly in the reference, models.py:836: `layers.{i}.freqs / scale.*` is all)
     return sd
 
 

@@ -1,7 +1,8 @@
-// The device side of the LDS-image tile loop (namespace chain).  Nine persistent kernels walk it: siren_forward_kernel
+// The device side of the LDS-image tile loop (namespace chain).  Ten persistent kernels walk it: siren_forward_kernel
 // and siren_backward_kernel (siren_chain.hip), modsiren_forward_kernel and modsiren_backward_kernel (modsiren.hip),
 // siren_gradient_kernel (siren_gradient.hip), modsiren_gradient_kernel (modsiren_gradient.hip), rff_forward_kernel,
-// rff_gradient_kernel and rff_backward_kernel (rff.hip).  Their epilogues
+// rff_gradient_kernel and rff_backward_kernel (rff.hip), gabor_forward_kernel (gabor.hip: the pair form of the
+// matrix step, one image fragment for two weight matrices).  Their epilogues
 // differ and stay with them; what they decide alike is written here once:
 //
 //   TileShape            the geometry of a tile for a hidden width
@@ -197,6 +198,40 @@ template <class S>
 __device__ __forceinline__ void mma_step(f32x16 (&acc)[S::NT], x3::Frag& fa, const float* a_row, int kc, const char* wb,
                                          const int (&boff)[S::NT]) {
   mma_chunk<S::NT, S::H>(acc, fa, kc + 1 < S::chunks ? a_row + (kc + 1) * kKc : nullptr, wb, boff);
+}
+// The pair form: acc0[t] += img W0^T and acc1[t] += img W1^T over one 16-deep chunk, the two weight chunks at wb0 / wb1
+// (the same layout, so one boff serves both).  The image fragment `fa` is read and split ONCE and feeds both products;
+// the next chunk's fragment is requested with the weight fragments and split behind the MFMAs, as in mma_chunk.
+template <int NT, int H>
+__device__ __forceinline__ void mma_chunk_pair(f32x16 (&acc0)[NT], f32x16 (&acc1)[NT], x3::Frag& fa,
+                                               const float* __restrict__ a_next, const char* __restrict__ wb0,
+                                               const char* __restrict__ wb1, const int (&boff)[NT]) {
+  x3::Frag fb0[NT], fb1[NT];
+#pragma unroll
+  for (int t = 0; t < NT; ++t) {
+    fb0[t].h = *reinterpret_cast<const x3::u32x4*>(wb0 + boff[t]);
+    fb0[t].m = *reinterpret_cast<const x3::u32x4*>(wb0 + H * 32 + boff[t]);
+    fb0[t].l = *reinterpret_cast<const x3::u32x4*>(wb0 + 2 * H * 32 + boff[t]);
+  }
+#pragma unroll
+  for (int t = 0; t < NT; ++t) {
+    fb1[t].h = *reinterpret_cast<const x3::u32x4*>(wb1 + boff[t]);
+    fb1[t].m = *reinterpret_cast<const x3::u32x4*>(wb1 + H * 32 + boff[t]);
+    fb1[t].l = *reinterpret_cast<const x3::u32x4*>(wb1 + 2 * H * 32 + boff[t]);
+  }
+  float4 n_lo = {0.f, 0.f, 0.f, 0.f}, n_hi = n_lo;
+  if (a_next) n_lo = *reinterpret_cast<const float4*>(a_next), n_hi = *reinterpret_cast<const float4*>(a_next + 8);
+#pragma unroll
+  for (int t = 0; t < NT; ++t) acc0[t] = mma6_32(fa, fb0[t], acc0[t]);
+#pragma unroll
+  for (int t = 0; t < NT; ++t) acc1[t] = mma6_32(fa, fb1[t], acc1[t]);
+  if (a_next) fa = split_octets(n_lo, n_hi);
+}
+template <class S>
+__device__ __forceinline__ void mma_step_pair(f32x16 (&acc0)[S::NT], f32x16 (&acc1)[S::NT], x3::Frag& fa,
+                                              const float* a_row, int kc, const char* wb0, const char* wb1,
+                                              const int (&boff)[S::NT]) {
+  mma_chunk_pair<S::NT, S::H>(acc0, acc1, fa, kc + 1 < S::chunks ? a_row + (kc + 1) * kKc : nullptr, wb0, wb1, boff);
 }
 // Scheduling pattern for a region of N MFMAs with LDS reads and vector work to hide beside them: after each of the
 // first four MFMAs READS_PER LDS reads, after each of the others VALU_PER vector instructions.

@@ -84,6 +84,29 @@ __device__ __forceinline__ void sincos_fast2(float u0, float u1, float* s0, floa
   sincos_fast2_core(u0, u1, s0, c0, s1, c1);
 }
 
+// The Gaussian envelope of a real Gabor layer (reference models.py:786-788: `scale = lin * scale_0`, then
+// `exp(-(scale**2))`): t = fl(fl(c s)^2) in the reference's order, then the library expf: at most 2 ulp of exp(-t)
+// of that float32 t while the result is a normal float, flushed towards 0 below.  +-inf gives 0, NaN gives NaN, as
+// torch.  (A bare v_exp_f32 of t log2(e) would not do: the rounding of the product grows with t.)
+__device__ __forceinline__ float gauss_envelope(float s, float c) {
+  const float sc = c * s;
+  return expf(-(sc * sc));
+}
+// cos(fl(w0 u)) exp(-fl(fl(c s)^2)) (models.py:785-788), the cosine on the fast path up to 8192 and the library's beyond
+__device__ __forceinline__ float gabor_f(float u, float s, float w0, float c) {
+  float sn, cs;
+  sincos_fast(w0 * u, &sn, &cs);
+  return cs * gauss_envelope(s, c);
+}
+// ... of two elements at once (sincos_fast2: the packed form, the same arithmetic)
+__device__ __forceinline__ void gabor_f2(float u0, float u1, float s0, float s1, float w0, float c, float* o0,
+                                         float* o1) {
+  float sn0, cs0, sn1, cs1;
+  sincos_fast2(w0 * u0, w0 * u1, &sn0, &cs0, &sn1, &cs1);
+  *o0 = cs0 * gauss_envelope(s0, c);
+  *o1 = cs1 * gauss_envelope(s1, c);
+}
+
 __device__ __forceinline__ float gelu_f(float z) {
   return 0.5f * z * (1.0f + erff(z * 0.70710678118654752440f));
 }

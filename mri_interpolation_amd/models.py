@@ -4,6 +4,7 @@ Mirrors reference `models.py`: `BaseMLP` (models.py:20-95), `Sine` (:108-114), `
 (:117-156), `SirenNet` (:160-233), `Modulator` / `ModulatedSirenNet` (:236-322), `HashMLP` (:658-754): same constructor arguments,
 `PsfSirenNet` (:397-539): same constructor arguments,
 `RffNet` (:542-584): same constructor arguments,
+`RealGaborLayer` (:757-788) / `GaborNet` (:836-885): same constructor arguments (the complex layer is refused),
 `forward(x)`, `training_step`, `predict_step`, `configure_optimizers`, same state-dict keys.
 Known defects of the reference are resolved to the INTENDED semantics:
   Q1  HashMLP.forward applies the decoder blocks in sequence (the reference calls a ModuleList);
@@ -550,6 +551,101 @@ class RffNet(BaseMLP):
             state_dict.pop(key)
         super()._load_from_state_dict(state_dict, prefix, local_metadata, strict, missing_keys,
                                       unexpected_keys, error_msgs)
+
+
+class RealGaborLayer(nn.Module):
+    """Real Gabor (WIRE) layer (reference models.py:757-788): two Linears on the same input, `freqs` and `scale`, and
+    cos(w0 freqs(x)) * exp(-(c scale(x))^2).  The Linears are the MFMA kernel with the identity epilogue, the
+    nonlinearity is one elementwise kernel (ops.gabor_activation); both are differentiable.  `is_first` and
+    `trainable` are kept for the reference's signature and change nothing, as there."""
+
+    def __init__(self, dim_in, dim_out, bias=True, is_first=False, w0=30.0, c=10.0, trainable=False):
+        super().__init__()
+        self.omega_0 = w0
+        self.scale_0 = c
+        self.is_first = is_first
+        self.dim_in = dim_in
+        self.freqs = FusedLinear(dim_in, dim_out, bias=bias)
+        self.scale = FusedLinear(dim_in, dim_out, bias=bias)
+
+    def forward(self, input):
+        return ops.gabor_activation(self.freqs(input), self.scale(input), self.omega_0, self.scale_0)
+
+
+class ComplexGaborLayer(nn.Module):
+    """The reference's complex Gabor layer (models.py:790-834) is not built: complex weights and activations have no
+    kernel here.  The name exists so that asking for it fails with a reason."""
+
+    def __init__(self, *args, **kwargs):
+        raise ValueError("ComplexGaborLayer is not supported: only real Gabor layers (RealGaborLayer) have kernels")
+
+
+class GaborNet(BaseMLP):
+    """Stack of Gabor layers (reference models.py:836-885): n_layers layers dim_in -> dim_hidden -> ... -> dim_out, the
+    last one a Gabor layer too (the output lies in (-1, 1]), every layer with c = sigma and the same w0.  State-dict keys
+    `layers.{i}.freqs.weight/bias` and `layers.{i}.scale.weight/bias`, as the reference's.
+    `forward` is the layer path (differentiable: training_step + autograd, and BaseMLP.forward_with_gradient).
+    Inference -- `predict_step`, and `forward` under torch.no_grad() in eval mode -- runs ONE kernel (ops.gabor_forward,
+    csrc/gabor.hip) where `_inference_plan` finds it serves; `fused_inference=False` keeps inference on the layer
+    path."""
+
+    def __init__(self, layer_cls=RealGaborLayer, dim_in: int = 3, dim_hidden: int = 128, dim_out: int = 1,
+                 n_layers: int = 4, sigma: float = 10.0, w0: float = 30.0, lr: float = 1e-4,
+                 fused_inference: bool = True):
+        if layer_cls is ComplexGaborLayer or getattr(layer_cls, "__name__", "") == "ComplexGaborLayer":
+            raise ValueError("GaborNet: ComplexGaborLayer is not supported (complex weights have no kernel); use "
+                             "RealGaborLayer")
+        if not (isinstance(layer_cls, type) and issubclass(layer_cls, RealGaborLayer)):
+            raise ValueError(f"GaborNet: layer_cls must be RealGaborLayer, got {layer_cls!r}")
+        if n_layers < 1:
+            raise ValueError(f"GaborNet: n_layers must be >= 1, got {n_layers}")
+        super().__init__(dim_in=dim_in, dim_out=dim_out, dim_hidden=dim_hidden, n_layers=n_layers, lr=lr,
+                         _build_layers=False)
+        self.layer_cls = layer_cls
+        self.sigma = sigma
+        self.w0 = w0
+        self.fused_inference = fused_inference
+        self.layers = nn.Sequential(*[
+            layer_cls(dim_in=dim_in if i == 0 else dim_hidden, dim_out=dim_out if i == n_layers - 1 else dim_hidden,
+                      c=sigma, w0=w0) for i in range(n_layers)])
+
+    def forward(self, x):
+        if not torch.is_grad_enabled() and not self.training:
+            plan = self._inference_plan(x)
+            if plan is not None:
+                return ops.gabor_forward(x, **plan)
+        return self.layers(x)
+
+    def predict_step(self, batch, batch_idx):
+        x, y = batch
+        plan = self._inference_plan(x)
+        if plan is not None:
+            with torch.no_grad():
+                return ops.gabor_forward(x.detach(), **plan)
+        return self(x)
+
+    def _inference_plan(self, x):
+        """Arguments of the fused inference kernel, or None where the layer path serves: a float32 (n, dim_in) tensor
+        on the GPU, real Gabor layers with one w0 and one c, biases everywhere, a shape the kernel takes."""
+        if not self.fused_inference or not x.is_cuda or x.dtype != torch.float32 or x.dim() != 2:
+            return None
+        ls = list(self.layers)
+        if len(ls) < 2 or any(type(l) is not RealGaborLayer for l in ls):
+            return None
+        if any(not isinstance(m, FusedLinear) or m.bias is None or m.activation_code != ops.ACT_IDENTITY
+               for l in ls for m in (l.freqs, l.scale)):
+            return None
+        if len({(float(l.omega_0), float(l.scale_0)) for l in ls}) != 1:
+            return None
+        hidden, dim_in = ls[0].freqs.weight.shape
+        want = [(hidden, dim_in)] + [(hidden, hidden)] * (len(ls) - 2) + [(1, hidden)]
+        if x.shape[1] != dim_in or any(m.weight.shape != shape for l, shape in zip(ls, want) for m in (l.freqs, l.scale)):
+            return None
+        if not ops.gabor_forward_supported(dim_in, hidden, len(ls), self.dim_out):
+            return None
+        return dict(freq_weights=[l.freqs.weight.detach() for l in ls], freq_biases=[l.freqs.bias.detach() for l in ls],
+                    scale_weights=[l.scale.weight.detach() for l in ls],
+                    scale_biases=[l.scale.bias.detach() for l in ls], w0=float(ls[0].omega_0), c=float(ls[0].scale_0))
 
 
 def psf_table(coordinates_spacing, n_sample: int, dim_in: int):

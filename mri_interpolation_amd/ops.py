@@ -654,6 +654,118 @@ def rff_backward(x, dy, b, weights, act, dz, d_weights, d_biases, ws=None):
               _ptr(ws), ws.numel() * 4, _stream())
 
 
+# --------------------------------------------------------------------------- real Gabor layers (GaborNet)
+def _gabor_pair(what, u, s):
+    if u.shape != s.shape or u.dim() < 1 or u.dtype != torch.float32 or s.dtype != torch.float32:
+        raise ValueError(f"{what}: u and s are float32 tensors of one shape, got {tuple(u.shape)} and {tuple(s.shape)}")
+    hidden = u.shape[-1]
+    return u.reshape(-1, hidden).contiguous(), s.reshape(-1, hidden).contiguous(), hidden
+
+
+def gabor_activation_forward(u, s, w0: float, c: float, out=None):
+    """out = cos(w0 u) exp(-(c s)^2) elementwise (csrc/gabor.hip); u, s (..., hidden)."""
+    _gpu(u, s, out)
+    u2, s2, hidden = _gabor_pair("gabor_activation", u, s)
+    if out is None:
+        out = torch.empty_like(u2)
+    if out.numel() != u2.numel() or not out.is_contiguous() or out.dtype != torch.float32:
+        raise ValueError("gabor_activation: out is a contiguous float32 tensor of u's size")
+    _lib.call("mri_gabor_activation", _ptr(u2), _ptr(s2), u2.shape[0], hidden, float(w0), float(c), _ptr(out), _stream())
+    return out.reshape(u.shape)
+
+
+def gabor_activation_backward(u, s, g, w0: float, c: float):
+    """(du, ds) of gabor_activation_forward from the gradient g of its output."""
+    _gpu(u, s, g)
+    u2, s2, hidden = _gabor_pair("gabor_activation_backward", u, s)
+    if g.shape != u.shape or g.dtype != torch.float32:
+        raise ValueError(f"gabor_activation_backward: g has u's shape {tuple(u.shape)}, got {tuple(g.shape)}")
+    g2 = g.reshape(-1, hidden).contiguous()
+    du, ds = torch.empty_like(u2), torch.empty_like(u2)
+    _lib.call("mri_gabor_activation_backward", _ptr(u2), _ptr(s2), _ptr(g2), u2.shape[0], hidden, float(w0), float(c),
+              _ptr(du), _ptr(ds), _stream())
+    return du.reshape(u.shape), ds.reshape(u.shape)
+
+
+class GaborActivationFunction(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, u, s, w0, c):
+        ctx.save_for_backward(u, s)
+        ctx.w0, ctx.c = w0, c
+        return gabor_activation_forward(u, s, w0, c)
+
+    @staticmethod
+    def backward(ctx, g):
+        u, s = ctx.saved_tensors
+        du, ds = gabor_activation_backward(u, s, g.contiguous(), ctx.w0, ctx.c)
+        return du, ds, None, None
+
+
+def gabor_activation(u, s, w0: float, c: float):
+    """cos(w0 u) exp(-(c s)^2), differentiable with respect to u and s (GaborActivationFunction)."""
+    return GaborActivationFunction.apply(u, s, float(w0), float(c))
+
+
+def gabor_forward_supported(dim_in: int, hidden: int, n_layers: int, dim_out: int) -> bool:
+    return bool(_lib.load().mri_gabor_forward_supported(dim_in, hidden, n_layers, dim_out))
+
+
+_gabor_ws = {}
+
+
+def _gabor_check(what, x, freq_weights, freq_biases, scale_weights, scale_biases, outputs):
+    """(n, dim_in, hidden, n_layers) of an inference call.  The library sees pointers only: a mismatched shape would be
+    read out of bounds on the device."""
+    if x.dim() != 2 or x.dtype != torch.float32:
+        raise ValueError(f"{what}: x is float32 (n, dim_in), got {x.dtype} {tuple(x.shape)}")
+    n, dim_in = x.shape
+    n_layers = len(freq_weights)
+    if n_layers < 2 or any(len(t) != n_layers for t in (freq_biases, scale_weights, scale_biases)):
+        raise ValueError(f"{what}: at least two layers, a freqs and a scale Linear with a bias each per layer")
+    hidden = freq_weights[0].shape[0]
+    want = [(hidden, dim_in)] + [(hidden, hidden)] * (n_layers - 2) + [(1, hidden)]
+    for name, ws, bs in (("freqs", freq_weights, freq_biases), ("scale", scale_weights, scale_biases)):
+        for i, (w, v, shape) in enumerate(zip(ws, bs, want)):
+            if tuple(w.shape) != shape or tuple(v.shape) != (shape[0],):
+                raise ValueError(f"{what}: {name} of layer {i} is {shape} with a bias of {shape[0]}, got "
+                                 f"{tuple(w.shape)} and {tuple(v.shape)}")
+    for t in list(outputs) + list(freq_weights) + list(freq_biases) + list(scale_weights) + list(scale_biases):
+        if not t.is_contiguous() or t.dtype != torch.float32:
+            raise ValueError(f"{what} needs contiguous float32 parameters and buffers")
+    return n, dim_in, hidden, n_layers
+
+
+def _gabor_scratch(device, need):
+    """The inference call's workspace (the split weights), one per device, grown on demand."""
+    ws = _gabor_ws.get(device.index)
+    if need > 0 and (ws is None or ws.numel() * 4 < need):
+        if ws is not None:
+            torch.cuda.synchronize(device)
+        ws = torch.empty((need + 3) // 4, dtype=torch.float32, device=device)
+        _gabor_ws[device.index] = ws
+    if ws is None:  # (two layers need none; an unsupported shape is refused by the library with its reason)
+        ws = torch.empty(64, dtype=torch.float32, device=device)
+    return ws
+
+
+def gabor_forward(x, freq_weights, freq_biases, scale_weights, scale_biases, w0: float, c: float, y=None):
+    """y (n, 1) = GaborNet(x) in one persistent kernel (csrc/gabor.hip): every layer cos(w0 freqs(a)) exp(-(c scale(a))^2),
+    the head included; nothing (n, hidden)-sized is written.  The four lists hold the layers' parameters, the head last."""
+    _gpu(x, y, *freq_weights, *freq_biases, *scale_weights, *scale_biases)
+    x = _rowmajor(x).contiguous()
+    if y is None:
+        y = torch.empty((x.shape[0], 1), device=x.device, dtype=torch.float32)
+    if y.numel() != x.shape[0]:
+        raise ValueError("gabor_forward: y holds n values")
+    n, dim_in, hidden, n_layers = _gabor_check("gabor_forward", x, freq_weights, freq_biases, scale_weights,
+                                               scale_biases, [y])
+    ws = _gabor_scratch(x.device, _lib.load().mri_gabor_forward_workspace_bytes(hidden, n_layers))
+    _lib.call("mri_gabor_forward", _ptr(x), n, dim_in, hidden, n_layers, _ptr_array(freq_weights),
+              _ptr_array(freq_biases), _ptr_array(scale_weights), _ptr_array(scale_biases), float(w0), float(c), _ptr(y),
+              _ptr(ws), ws.numel() * 4, _stream())
+    return y
+
+
 # --------------------------------------------------------------------------- fused tiny MLP
 def tiny_mlp_supported(k_in: int, hidden: int, dim_out: int) -> bool:
     return bool(_lib.load().mri_tiny_mlp_supported(k_in, hidden, dim_out))

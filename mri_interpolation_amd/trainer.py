@@ -175,6 +175,9 @@ def fusable_layers(model, batch_norm: bool = False, modulated: bool = False, rff
     ModulatedPlan (both stacks; ValueError with the reason for what csrc/modsiren.hip does not cover).  `rff`: an
     RffNet gives its RffPlan (ValueError with the reason for what csrc/rff.hip does not cover)."""
     enc, layers = None, []
+    if isinstance(model, models.GaborNet):
+        # a layer is two Linears and an elementwise product: training_step + autograd over the HIP ops
+        return None
     if isinstance(model, models.RffNet):
         # without the keyword it runs training_step + autograd over the HIP ops
         return _rff_plan(model) if rff else None
@@ -240,6 +243,9 @@ class FusedStep:
                  batch_norm: bool = False, modulated: bool = False, rff: bool = False):
         plan = fusable_layers(model, batch_norm=batch_norm, modulated=modulated, rff=rff)
         if plan is None:
+            if isinstance(model, models.GaborNet):
+                raise ValueError("GaborNet has no fused training step: it trains through training_step + autograd "
+                                 "(csrc/gabor.hip has the layer kernels and the fused inference kernel)")
             raise ValueError("model is not a fusable chain")
         # BatchNorm plan (csrc/batchnorm.hip): per block linear_fwd -> bn_stats -> bn_act_forward, and
         # bn_act_backward in front of the Linear's backward kernels
@@ -1201,6 +1207,9 @@ class SteadyLoop:
 
     @staticmethod
     def unsupported(step: "FusedStep", pipe: BatchPipeline) -> Optional[str]:
+        if step is None:  # what Trainer holds for such a model (FusedStep refuses it)
+            return ("the model has no fused step (GaborNet, and every model on the autograd path, trains through "
+                    "training_step + autograd), so there is nothing to queue natively")
         ld = pipe.loader
         if step.psf is not None:
             return "PsfSirenNet: the PSF step runs eagerly (FusedStep.train_step), it has no native form"
