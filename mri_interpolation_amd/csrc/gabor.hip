@@ -23,6 +23,7 @@
 #include "bf16x3.h"
 #include "common.h"
 #include "device_math.h"
+#include "entry_args.h"
 #include "siren_chain.h"
 
 namespace mri {
@@ -212,25 +213,29 @@ __global__ __launch_bounds__(kThreads) void gabor_forward_kernel(const GaborArgs
 }
 
 // ------------------------------------------------------------------------------------------------------ host side
+// the fused chain's shape rule, each argument refused by name
+int check_gabor_shape(const char* what, int dim_in, int hidden, int n_layers, int dim_out) {
+  MRI_REQUIRE(hidden == 64 || hidden == 128, "%s: hidden = %d is not supported (64 / 128)", what, hidden);
+  MRI_REQUIRE(dim_in >= 1 && dim_in <= kFwdIn, "%s: dim_in = %d is not supported (1 .. %d)", what, dim_in, kFwdIn);
+  MRI_REQUIRE(n_layers >= 2 && n_layers <= kMaxSine, "%s: n_layers = %d is not supported (2 .. %d)", what, n_layers,
+              kMaxSine);
+  MRI_REQUIRE(dim_out == 1, "%s: dim_out = %d is not supported (1)", what, dim_out);
+  return MRI_OK;
+}
 bool gabor_supported(int dim_in, int hidden, int n_layers, int dim_out) {
-  return (hidden == 64 || hidden == 128) && dim_in >= 1 && dim_in <= kFwdIn && n_layers >= 2 && n_layers <= kMaxSine &&
-         dim_out == 1;
+  return check_gabor_shape("fused Gabor forward", dim_in, hidden, n_layers, dim_out) == MRI_OK;
 }
 // the freqs / scale pair of every H x H layer
 int64_t gabor_split_bytes(int hidden, int n_layers) { return (int64_t)2 * (n_layers - 2) * split_matrix_bytes(hidden); }
 
 int check_activation(const char* what, const float* u, const float* s, int64_t n, int hidden, float w0, float c) {
   MRI_REQUIRE(hidden >= 1, "%s: hidden = %d is not supported (>= 1)", what, hidden);
-  MRI_REQUIRE(n >= 0 && n < (1ll << 31), "n = %lld out of range", (long long)n);
+  MRI_CHECK(check_rows(n));
   MRI_REQUIRE(n * hidden < (1ll << 38), "n * hidden = %lld out of range (one launch)", (long long)(n * hidden));
-  MRI_REQUIRE(std::isfinite(w0), "%s: w0 is not finite", what);
-  MRI_REQUIRE(std::isfinite(c), "%s: c is not finite", what);
+  MRI_CHECK(check_finite(what, "w0", w0));
+  MRI_CHECK(check_finite(what, "c", c));
   if (n == 0) return MRI_OK;
-  MRI_REQUIRE(u, "u is NULL");
-  MRI_REQUIRE(s, "s is NULL");
-  MRI_REQUIRE(aligned_to(u, 4), "u must be 4-byte aligned");
-  MRI_REQUIRE(aligned_to(s, 4), "s must be 4-byte aligned");
-  return MRI_OK;
+  return check_buffers({{"u", u}, {"s", s}}, 4);
 }
 
 }  // namespace
@@ -240,10 +245,9 @@ using namespace mri;
 
 extern "C" int mri_gabor_activation(const float* u, const float* s, int64_t n, int32_t hidden, float w0, float c,
                                     float* out, void* stream) {
-  if (int rc = check_activation("Gabor activation", u, s, n, hidden, w0, c)) return rc;
+  MRI_CHECK(check_activation("Gabor activation", u, s, n, hidden, w0, c));
   if (n == 0) return MRI_OK;
-  MRI_REQUIRE(out, "out is NULL");
-  MRI_REQUIRE(aligned_to(out, 4), "out must be 4-byte aligned");
+  MRI_CHECK(check_buffer("out", out, 4));
   const int64_t count = n * hidden;
   hipLaunchKernelGGL(gabor_activation_kernel, dim3((unsigned)ceil_div(count, 256)), dim3(256), 0, (hipStream_t)stream, u,
                      s, count, w0, c, out);
@@ -252,14 +256,9 @@ extern "C" int mri_gabor_activation(const float* u, const float* s, int64_t n, i
 
 extern "C" int mri_gabor_activation_backward(const float* u, const float* s, const float* g, int64_t n, int32_t hidden,
                                              float w0, float c, float* du, float* ds, void* stream) {
-  if (int rc = check_activation("Gabor activation backward", u, s, n, hidden, w0, c)) return rc;
+  MRI_CHECK(check_activation("Gabor activation backward", u, s, n, hidden, w0, c));
   if (n == 0) return MRI_OK;
-  MRI_REQUIRE(g, "g is NULL");
-  MRI_REQUIRE(du, "du is NULL");
-  MRI_REQUIRE(ds, "ds is NULL");
-  MRI_REQUIRE(aligned_to(g, 4), "g must be 4-byte aligned");
-  MRI_REQUIRE(aligned_to(du, 4), "du must be 4-byte aligned");
-  MRI_REQUIRE(aligned_to(ds, 4), "ds must be 4-byte aligned");
+  MRI_CHECK(check_buffers({{"g", g}, {"du", du}, {"ds", ds}}, 4));
   const int64_t count = n * hidden;
   hipLaunchKernelGGL(gabor_activation_backward_kernel, dim3((unsigned)ceil_div(count, 256)), dim3(256), 0,
                      (hipStream_t)stream, u, s, g, count, w0, c, du, ds);
@@ -279,40 +278,22 @@ extern "C" int mri_gabor_forward(const float* x, int64_t n, int32_t dim_in, int3
                                  const float* const* freq_weight, const float* const* freq_bias,
                                  const float* const* scale_weight, const float* const* scale_bias, float w0, float c,
                                  float* y, void* workspace, int64_t workspace_bytes, void* stream) {
-  MRI_REQUIRE(hidden == 64 || hidden == 128, "fused Gabor forward: hidden = %d is not supported (64 / 128)", hidden);
-  MRI_REQUIRE(dim_in >= 1 && dim_in <= kFwdIn, "fused Gabor forward: dim_in = %d is not supported (1 .. %d)", dim_in,
-              kFwdIn);
-  MRI_REQUIRE(n_layers >= 2 && n_layers <= kMaxSine, "fused Gabor forward: n_layers = %d is not supported (2 .. %d)",
-              n_layers, kMaxSine);
-  MRI_REQUIRE(std::isfinite(w0), "fused Gabor forward: w0 is not finite");
-  MRI_REQUIRE(std::isfinite(c), "fused Gabor forward: c is not finite");
-  MRI_REQUIRE(n >= 0 && n < (1ll << 31), "n = %lld out of range", (long long)n);
+  const char* const what = "fused Gabor forward";
+  MRI_CHECK(check_gabor_shape(what, dim_in, hidden, n_layers, 1));
+  MRI_CHECK(check_finite(what, "w0", w0));
+  MRI_CHECK(check_finite(what, "c", c));
+  MRI_CHECK(check_rows(n));
   if (n == 0) return MRI_OK;
-  MRI_REQUIRE(x, "x is NULL");
-  MRI_REQUIRE(y, "y is NULL");
-  MRI_REQUIRE(freq_weight, "freq_weight is NULL");
-  MRI_REQUIRE(freq_bias, "freq_bias is NULL");
-  MRI_REQUIRE(scale_weight, "scale_weight is NULL");
-  MRI_REQUIRE(scale_bias, "scale_bias is NULL");
-  MRI_REQUIRE(aligned_to(x, 4), "x must be 4-byte aligned");
-  MRI_REQUIRE(aligned_to(y, 4), "y must be 4-byte aligned");
-  const int64_t need = gabor_split_bytes(hidden, n_layers);
-  MRI_REQUIRE(need == 0 || (workspace && workspace_bytes >= need && aligned_to(workspace, 16)),
-              "workspace: the fused Gabor forward needs %lld bytes, 16-byte aligned (mri_gabor_forward_workspace_bytes)",
-              (long long)need);
+  MRI_CHECK(check_buffers({{"x", x}, {"y", y}}, 4));
+  MRI_CHECK(check_buffers({{"freq_weight", freq_weight}, {"freq_bias", freq_bias}, {"scale_weight", scale_weight},
+                           {"scale_bias", scale_bias}}, kAnyAlignment));
+  MRI_CHECK(check_workspace(what, "mri_gabor_forward_workspace_bytes", workspace, workspace_bytes,
+                            gabor_split_bytes(hidden, n_layers)));
+  MRI_CHECK(check_pointers({{"freq_weight", freq_weight}, {"freq_bias", freq_bias}, {"scale_weight", scale_weight},
+                            {"scale_bias", scale_bias}}, 0, n_layers, 4));
   GaborArgs a{};
   a.x = x, a.n = n, a.dim_in = dim_in, a.L = n_layers, a.w0 = w0, a.c = c, a.y = y;
-  for (int l = 0; l < n_layers; ++l) {
-    MRI_REQUIRE(freq_weight[l], "freq_weight[%d] is NULL", l);
-    MRI_REQUIRE(freq_bias[l], "freq_bias[%d] is NULL", l);
-    MRI_REQUIRE(scale_weight[l], "scale_weight[%d] is NULL", l);
-    MRI_REQUIRE(scale_bias[l], "scale_bias[%d] is NULL", l);
-    MRI_REQUIRE(aligned_to(freq_weight[l], 4) && aligned_to(freq_bias[l], 4),
-                "freq_weight[%d] / freq_bias[%d] must be 4-byte aligned", l, l);
-    MRI_REQUIRE(aligned_to(scale_weight[l], 4) && aligned_to(scale_bias[l], 4),
-                "scale_weight[%d] / scale_bias[%d] must be 4-byte aligned", l, l);
-    a.bias_f[l] = freq_bias[l], a.bias_s[l] = scale_bias[l];
-  }
+  for (int l = 0; l < n_layers; ++l) a.bias_f[l] = freq_bias[l], a.bias_s[l] = scale_bias[l];
   a.wf0 = freq_weight[0], a.ws0 = scale_weight[0];
   a.wf_head = freq_weight[n_layers - 1], a.ws_head = scale_weight[n_layers - 1];
   a.wsplit = static_cast<const char*>(workspace);
@@ -324,8 +305,7 @@ extern "C" int mri_gabor_forward(const float* x, int64_t n, int32_t dim_in, int3
   if (int rc = split_weights_ld(scale_weight + 1, n_layers - 2, hidden, hidden, false, out + smb, 2 * smb, st)) return rc;
   return dispatch_hidden_mod(hidden, [&](auto h) {
     using S = GShape<decltype(h)::value>;
-    const int blocks = (int)std::min<int64_t>(ceil_div(n, S::rows), 256);  // one workgroup per CU
-    hipLaunchKernelGGL((gabor_forward_kernel<S>), dim3(blocks), dim3(kThreads), 0, st, a);
+    hipLaunchKernelGGL((gabor_forward_kernel<S>), dim3(persistent_blocks(n, S::rows)), dim3(kThreads), 0, st, a);
     return check_launch("gabor_forward_kernel");
   });
 }

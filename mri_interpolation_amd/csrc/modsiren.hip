@@ -24,6 +24,7 @@
 #include "bf16x3.h"
 #include "common.h"
 #include "device_math.h"
+#include "entry_args.h"
 #include "siren_chain.h"
 
 namespace mri {
@@ -501,16 +502,19 @@ __global__ __launch_bounds__(kThreads) void modsiren_backward_kernel(const ModBw
 }
 
 // ------------------------------------------------------------------------------------------------------ host side
-bool mod_supported(int dim_in, int hidden, int n_layers, int dim_out) {
-  return (hidden == 64 || hidden == 128) && dim_in >= 1 && dim_in <= kMaxIn && n_layers >= 2 &&
-         n_layers <= kMaxSine && dim_out == 1;
+int check_mod_shape(int dim_in, int hidden, int n_layers, int dim_out) {
+  MRI_REQUIRE((hidden == 64 || hidden == 128) && dim_in >= 1 && dim_in <= kMaxIn && n_layers >= 2 &&
+                  n_layers <= kMaxSine && dim_out == 1,
+              "fused modulated SIREN: %d -> %d x %d -> %d is not supported (hidden 64 / 128, 1 <= dim_in <= 8, "
+              "2 <= n_layers <= %d, dim_out 1)", dim_in, hidden, n_layers, dim_out, kMaxSine);
+  return MRI_OK;
 }
-const char* kUnsupported =
-    "fused modulated SIREN: %d -> %d x %d -> %d is not supported (hidden 64 / 128, 1 <= dim_in <= 8, "
-    "2 <= n_layers <= %d, dim_out 1)";
+bool mod_supported(int dim_in, int hidden, int n_layers, int dim_out) {
+  return check_mod_shape(dim_in, hidden, n_layers, dim_out) == MRI_OK;
+}
 
 int mod_tile_rows(int hidden) { return hidden == 128 ? 64 : 128; }
-int mod_blocks(int hidden, int64_t n) { return (int)std::min<int64_t>(ceil_div(n, mod_tile_rows(hidden)), 256); }
+int mod_blocks(int hidden, int64_t n) { return persistent_blocks(n, mod_tile_rows(hidden)); }
 int64_t mod_split_bytes(int hidden, int L) { return 2 * (int64_t)(L - 1) * split_matrix_bytes(hidden); }
 int64_t mod_slab_bytes(int64_t n, int hidden, int L) {
   const int64_t chain = std::max<int64_t>((int64_t)mod_blocks(hidden, n) * ModBwdSlab{hidden, L}.floats(), 256);
@@ -535,30 +539,26 @@ int launch_mod_forward(int hidden, const ModArgs& a, int mode, hipStream_t st) {
   });
 }
 
+// the four saved (n, hidden) tensors per layer (the backward's weight-gradient kernels stream act / hid in 16-byte pieces:
+// one contract for the four, in the forward too)
+int check_saved(const void* act, const void* hid, const void* dcos, const void* sn, int L) {
+  return check_pointers({{"act", act}, {"hid", hid}, {"dcos", dcos}, {"sn", sn}}, 0, L, 16);
+}
+
 // the checks and the argument block the three forward entry points share
 int fill_forward(ModArgs& a, const float* x, int64_t n, int dim_in, int hidden, int L, const float* const* sw,
                  const float* const* sb, const float* const* mw, const float* const* mb, float w0_first, float w0,
                  float* const* act, float* const* hid, float* const* dcos, float* const* sn, float* y, bool train) {
-  MRI_REQUIRE(x && sw && sb && mw && mb && y, "NULL pointer");
+  MRI_CHECK(check_buffers({{"x", x}, {"siren_weight", sw}, {"siren_bias", sb}, {"mod_weight", mw}, {"mod_bias", mb},
+                           {"y", y}}, kAnyAlignment));
   a.x = x, a.n = n, a.dim_in = dim_in, a.L = L, a.w0_first = w0_first, a.w0 = w0, a.y = y;
-  for (int l = 0; l <= L; ++l) {
-    MRI_REQUIRE(sw[l] && sb[l], "NULL SIREN parameter pointer (layer %d)", l);
-    a.ws[l] = sw[l], a.bs[l] = sb[l];
-  }
-  for (int l = 0; l < L; ++l) {
-    MRI_REQUIRE(mw[l] && mb[l], "NULL modulator parameter pointer (layer %d)", l);
-    a.wm[l] = mw[l], a.bm[l] = mb[l];
-  }
-  if (train) {
-    MRI_REQUIRE(act && hid && dcos && sn, "training needs the act / hid / dcos / sn buffer arrays");
-    for (int l = 0; l < L; ++l) {
-      MRI_REQUIRE(act[l] && hid[l] && dcos[l] && sn[l], "NULL saved-tensor buffer (layer %d)", l);
-      // (the backward's weight-gradient kernels stream act / hid in 16-byte pieces: one contract for the four, here too)
-      MRI_REQUIRE(aligned_to(act[l], 16) && aligned_to(hid[l], 16) && aligned_to(dcos[l], 16) && aligned_to(sn[l], 16),
-                  "act / hid / dcos / sn buffers must be 16-byte aligned (layer %d)", l);
-      a.act[l] = act[l], a.hid[l] = hid[l], a.dcos[l] = dcos[l], a.sn[l] = sn[l];
-    }
-  }
+  MRI_CHECK(check_pointers({{"siren_weight", sw}, {"siren_bias", sb}}, 0, L + 1, kAnyAlignment));
+  MRI_CHECK(check_pointers({{"mod_weight", mw}, {"mod_bias", mb}}, 0, L, kAnyAlignment));
+  for (int l = 0; l <= L; ++l) a.ws[l] = sw[l], a.bs[l] = sb[l];
+  for (int l = 0; l < L; ++l) a.wm[l] = mw[l], a.bm[l] = mb[l];
+  if (!train) return MRI_OK;
+  MRI_CHECK(check_saved(act, hid, dcos, sn, L));
+  for (int l = 0; l < L; ++l) a.act[l] = act[l], a.hid[l] = hid[l], a.dcos[l] = dcos[l], a.sn[l] = sn[l];
   return MRI_OK;
 }
 
@@ -587,14 +587,12 @@ extern "C" int mri_modsiren_forward(const float* x, int64_t n, int32_t dim_in, i
                                     float w0, float* const* act, float* const* hid, float* const* dcos,
                                     float* const* sn, float* y, void* workspace, int64_t workspace_bytes,
                                     void* stream) {
-  MRI_REQUIRE(mod_supported(dim_in, hidden, n_layers, 1), kUnsupported, dim_in, hidden, n_layers, 1, kMaxSine);
-  MRI_REQUIRE(n >= 0 && n < (1ll << 31), "n = %lld out of range", (long long)n);
+  MRI_CHECK(check_mod_shape(dim_in, hidden, n_layers, 1));
+  MRI_CHECK(check_rows(n));
   if (n == 0) return MRI_OK;
   const bool train = act || hid || dcos || sn;
-  const int64_t need = mod_split_bytes(hidden, n_layers);
-  MRI_REQUIRE(workspace && workspace_bytes >= need && aligned_to(workspace, 16),
-              "modulated SIREN forward needs a 16-byte aligned workspace of %lld bytes "
-              "(mri_modsiren_forward_workspace_bytes)", (long long)need);
+  MRI_CHECK(check_workspace("modulated SIREN forward", "mri_modsiren_forward_workspace_bytes", workspace,
+                            workspace_bytes, mod_split_bytes(hidden, n_layers)));
   ModArgs a{};
   if (int rc = fill_forward(a, x, n, dim_in, hidden, n_layers, siren_weight, siren_bias, mod_weight, mod_bias,
                             w0_first, w0, act, hid, dcos, sn, y, train))
@@ -613,14 +611,12 @@ extern "C" int mri_modsiren_forward_loss(const float* x, const float* target, in
                                          float w0_first, float w0, float grad_divisor, float* const* act,
                                          float* const* hid, float* const* dcos, float* const* sn, float* y, float* dy,
                                          float* loss_out, void* workspace, int64_t workspace_bytes, void* stream) {
-  MRI_REQUIRE(mod_supported(dim_in, hidden, n_layers, 1), kUnsupported, dim_in, hidden, n_layers, 1, kMaxSine);
-  MRI_REQUIRE(n >= 0 && n < (1ll << 31) && n_total >= n && grad_divisor > 0.f, "bad n / n_total / divisor");
+  MRI_CHECK(check_mod_shape(dim_in, hidden, n_layers, 1));
+  MRI_CHECK(check_batch_slice(n, n_total, grad_divisor));
   if (n == 0) return MRI_OK;
-  MRI_REQUIRE(target && dy && loss_out, "NULL pointer");
-  const int64_t need = mri_modsiren_backward_workspace_bytes(n, hidden, n_layers);
-  MRI_REQUIRE(workspace && workspace_bytes >= need && aligned_to(workspace, 16),
-              "modulated SIREN forward with loss needs a 16-byte aligned workspace of %lld bytes "
-              "(mri_modsiren_backward_workspace_bytes)", (long long)need);
+  MRI_CHECK(check_buffers({{"target", target}, {"dy", dy}, {"loss_out", loss_out}}, kAnyAlignment));
+  MRI_CHECK(check_workspace("modulated SIREN forward with loss", "mri_modsiren_backward_workspace_bytes", workspace,
+                            workspace_bytes, mri_modsiren_backward_workspace_bytes(n, hidden, n_layers)));
   ModArgs a{};
   if (int rc = fill_forward(a, x, n, dim_in, hidden, n_layers, siren_weight, siren_bias, mod_weight, mod_bias,
                             w0_first, w0, act, hid, dcos, sn, y, true))
@@ -645,32 +641,26 @@ extern "C" int mri_modsiren_backward(const float* x, const float* dy, int64_t n,
                                      float* const* d_siren_bias, float* const* d_mod_weight,
                                      float* const* d_mod_bias, void* workspace, int64_t workspace_bytes,
                                      void* stream) {
-  MRI_REQUIRE(mod_supported(dim_in, hidden, n_layers, 1), kUnsupported, dim_in, hidden, n_layers, 1, kMaxSine);
-  MRI_REQUIRE(n >= 0 && n < (1ll << 31), "n = %lld out of range", (long long)n);
+  MRI_CHECK(check_mod_shape(dim_in, hidden, n_layers, 1));
+  MRI_CHECK(check_rows(n));
   if (n == 0) return MRI_OK;
-  MRI_REQUIRE(x && dy && siren_weight && mod_weight && act && hid && dcos && sn && dzs && dzm && d_siren_weight &&
-                  d_siren_bias && d_mod_weight && d_mod_bias, "NULL pointer");
   const int L = n_layers;
-  const int64_t need = mri_modsiren_backward_workspace_bytes(n, hidden, L);
-  MRI_REQUIRE(workspace && workspace_bytes >= need && aligned_to(workspace, 16),
-              "modulated SIREN backward needs a 16-byte aligned workspace of %lld bytes "
-              "(mri_modsiren_backward_workspace_bytes)", (long long)need);
+  MRI_CHECK(check_buffers({{"x", x}, {"dy", dy}, {"siren_weight", siren_weight}, {"mod_weight", mod_weight},
+                           {"act", act}, {"hid", hid}, {"dcos", dcos}, {"sn", sn}, {"dzs", dzs}, {"dzm", dzm},
+                           {"d_siren_weight", d_siren_weight}, {"d_siren_bias", d_siren_bias},
+                           {"d_mod_weight", d_mod_weight}, {"d_mod_bias", d_mod_bias}}, kAnyAlignment));
+  MRI_CHECK(check_workspace("modulated SIREN backward", "mri_modsiren_backward_workspace_bytes", workspace,
+                            workspace_bytes, mri_modsiren_backward_workspace_bytes(n, hidden, L)));
+  MRI_CHECK(check_pointers({{"siren_weight", siren_weight}, {"d_siren_weight", d_siren_weight},
+                            {"d_siren_bias", d_siren_bias}}, 0, L + 1, kAnyAlignment));
+  MRI_CHECK(check_pointers({{"mod_weight", mod_weight}, {"d_mod_weight", d_mod_weight}, {"d_mod_bias", d_mod_bias}}, 0,
+                           L, kAnyAlignment));
+  MRI_CHECK(check_saved(act, hid, dcos, sn, L));
+  MRI_CHECK(check_pointers({{"dzs", dzs}, {"dzm", dzm}}, 1, L - 1, 16));
   ModBwdArgs a{};
   a.x = x, a.dy = dy, a.n = n, a.dim_in = dim_in, a.L = L;
-  for (int l = 0; l <= L; ++l)
-    MRI_REQUIRE(siren_weight[l] && d_siren_weight[l] && d_siren_bias[l],
-                "NULL SIREN parameter / gradient pointer (layer %d)", l);
-  for (int l = 0; l < L; ++l) {
-    MRI_REQUIRE(mod_weight[l] && d_mod_weight[l] && d_mod_bias[l],
-                "NULL modulator parameter / gradient pointer (layer %d)", l);
-    MRI_REQUIRE(act[l] && hid[l] && dcos[l] && sn[l] && (l == 0 || (dzs[l] && dzm[l])),
-                "NULL saved-tensor buffer (layer %d)", l);
-    MRI_REQUIRE(aligned_to(act[l], 16) && aligned_to(hid[l], 16) && aligned_to(dcos[l], 16) && aligned_to(sn[l], 16),
-                "act / hid / dcos / sn buffers must be 16-byte aligned (layer %d)", l);
-    MRI_REQUIRE(l == 0 || (aligned_to(dzs[l], 16) && aligned_to(dzm[l], 16)), "dzs / dzm buffers must be 16-byte aligned (layer %d)",
-                l);
+  for (int l = 0; l < L; ++l)
     a.hid[l] = hid[l], a.dcos[l] = dcos[l], a.sn[l] = sn[l], a.dzs[l] = dzs[l], a.dzm[l] = dzm[l];
-  }
   a.w_head = siren_weight[L], a.act_last = act[L - 1];
   a.partial = static_cast<float*>(workspace);
   char* const wtsplit = static_cast<char*>(workspace) + mod_slab_bytes(n, hidden, L);

@@ -27,6 +27,7 @@
 #include "bf16x3.h"
 #include "common.h"
 #include "device_math.h"
+#include "entry_args.h"
 #include "siren_chain.h"
 
 namespace mri {
@@ -36,7 +37,6 @@ using namespace chain;
 
 constexpr int kSlots = 4;         // image rows of a point: value, d/dx_0, d/dx_1, d/dx_2
 constexpr int kGradIn = 3;        // axes the slots hold
-constexpr int kMaxBlocks = 256;   // one workgroup per CU
 
 // Geometry of modsiren.hip's MShape (a wave owns a 32 x 32 tile of BOTH layer outputs), the rows counted in points of
 // four image rows: 64 rows = 16 points at H = 128, 128 rows = 32 points at H = 64.
@@ -223,8 +223,17 @@ __global__ __launch_bounds__(kThreads) void modsiren_gradient_kernel(const MGrad
   }
 }
 
+// the shapes of the fused training step (modsiren.hip) with at most kGradIn axes, each argument refused by name
+int check_mgrad_shape(const char* what, int dim_in, int hidden, int n_layers, int dim_out) {
+  MRI_REQUIRE(hidden == 64 || hidden == 128, "%s: hidden = %d is not supported (64 / 128)", what, hidden);
+  MRI_REQUIRE(dim_in >= 1 && dim_in <= kGradIn, "%s: dim_in = %d is not supported (1 .. %d)", what, dim_in, kGradIn);
+  MRI_REQUIRE(n_layers >= 2 && n_layers <= kMaxSine, "%s: n_layers = %d is not supported (2 .. %d)", what, n_layers,
+              kMaxSine);
+  MRI_REQUIRE(dim_out == 1, "%s: dim_out = %d is not supported (1)", what, dim_out);
+  return MRI_OK;
+}
 bool mgrad_supported(int dim_in, int hidden, int n_layers, int dim_out) {
-  return dim_in <= kGradIn && mri_modsiren_supported(dim_in, hidden, n_layers, dim_out) != 0;
+  return check_mgrad_shape("modulated SIREN gradient", dim_in, hidden, n_layers, dim_out) == MRI_OK;
 }
 
 int64_t mgrad_split_bytes(int hidden, int L) { return 2 * (int64_t)(L - 1) * split_matrix_bytes(hidden); }
@@ -232,8 +241,7 @@ int64_t mgrad_split_bytes(int hidden, int L) { return 2 * (int64_t)(L - 1) * spl
 template <int H>
 int launch_mgrad(const MGradArgs& a, hipStream_t st) {
   using S = MGradShape<H>;
-  const int blocks = (int)std::min<int64_t>(ceil_div(a.n, S::points), kMaxBlocks);
-  hipLaunchKernelGGL((modsiren_gradient_kernel<S>), dim3(blocks), dim3(kThreads), 0, st, a);
+  hipLaunchKernelGGL((modsiren_gradient_kernel<S>), dim3(persistent_blocks(a.n, S::points)), dim3(kThreads), 0, st, a);
   return check_launch("modsiren_gradient_kernel");
 }
 
@@ -256,34 +264,27 @@ extern "C" int mri_modsiren_gradient(const float* x, int64_t n, int32_t dim_in, 
                                      const float* const* mod_weight, const float* const* mod_bias, float w0_first,
                                      float w0, float* y, float* dydx, void* workspace, int64_t workspace_bytes,
                                      void* stream) {
-  MRI_REQUIRE(hidden == 64 || hidden == 128, "modulated SIREN gradient: hidden = %d is not supported (64 / 128)",
-              hidden);
-  MRI_REQUIRE(dim_in >= 1 && dim_in <= kGradIn, "modulated SIREN gradient: dim_in = %d is not supported (1 .. %d)",
-              dim_in, kGradIn);
-  MRI_REQUIRE(n_layers >= 2 && n_layers <= kMaxSine, "modulated SIREN gradient: n_layers = %d is not supported (2 .. %d)",
-              n_layers, kMaxSine);
-  MRI_REQUIRE(mgrad_supported(dim_in, hidden, n_layers, 1), "modulated SIREN gradient: %d -> %d x %d -> 1 is not supported",
-              dim_in, hidden, n_layers);
-  if (int rc = check_gradient_io(x, n, y, dydx)) return rc;
+  const char* const what = "modulated SIREN gradient";
+  MRI_CHECK(check_mgrad_shape(what, dim_in, hidden, n_layers, 1));
+  MRI_CHECK(check_gradient_io(x, n, y, dydx));
   if (n == 0) return MRI_OK;
-  MRI_REQUIRE(siren_weight && siren_bias, "siren_weight / siren_bias is NULL");
-  MRI_REQUIRE(mod_weight && mod_bias, "mod_weight / mod_bias is NULL");
-  const int64_t need = mgrad_split_bytes(hidden, n_layers);
-  MRI_REQUIRE(workspace && workspace_bytes >= need && aligned_to(workspace, 16),
-              "workspace: the modulated SIREN gradient needs %lld bytes, 16-byte aligned "
-              "(mri_modsiren_gradient_workspace_bytes)", (long long)need);
+  MRI_CHECK(check_buffers({{"siren_weight", siren_weight}, {"siren_bias", siren_bias}, {"mod_weight", mod_weight},
+                           {"mod_bias", mod_bias}}, kAnyAlignment));
+  MRI_CHECK(check_workspace(what, "mri_modsiren_gradient_workspace_bytes", workspace, workspace_bytes,
+                            mgrad_split_bytes(hidden, n_layers)));
+  // (a NULL entry keeps this entry point's first wording, which says which of the two networks and which layer)
+  for (int l = 0; l <= n_layers; ++l)
+    MRI_REQUIRE(siren_weight[l] && siren_bias[l], "NULL SIREN parameter pointer (layer %d)", l);
+  MRI_CHECK(check_pointers({{"siren_weight", siren_weight}}, 0, n_layers + 1, 16));
+  for (int l = 0; l < n_layers; ++l)
+    MRI_REQUIRE(mod_weight[l] && mod_bias[l], "NULL modulator parameter pointer (layer %d)", l);
+  MRI_CHECK(check_pointers({{"mod_weight", mod_weight}}, 0, n_layers, 16));
   MGradArgs a{};
   a.x = x, a.n = n, a.dim_in = dim_in, a.L = n_layers, a.w0_first = w0_first, a.w0 = w0, a.y = y, a.dydx = dydx;
-  for (int l = 0; l <= n_layers; ++l) {
-    MRI_REQUIRE(siren_weight[l] && siren_bias[l], "NULL SIREN parameter pointer (layer %d)", l);
-    MRI_REQUIRE(aligned_to(siren_weight[l], 16), "siren_weight[%d] must be 16-byte aligned", l);
-    a.ws[l] = siren_weight[l], a.bs[l] = siren_bias[l];
-  }
-  for (int l = 0; l < n_layers; ++l) {
-    MRI_REQUIRE(mod_weight[l] && mod_bias[l], "NULL modulator parameter pointer (layer %d)", l);
-    MRI_REQUIRE(aligned_to(mod_weight[l], 16), "mod_weight[%d] must be 16-byte aligned", l);
-    a.wm[l] = mod_weight[l], a.bm[l] = mod_bias[l];
-  }
+  std::copy(siren_weight, siren_weight + n_layers + 1, a.ws);
+  std::copy(siren_bias, siren_bias + n_layers + 1, a.bs);
+  std::copy(mod_weight, mod_weight + n_layers, a.wm);
+  std::copy(mod_bias, mod_bias + n_layers, a.bm);
   a.wsplit = static_cast<const char*>(workspace);
   hipStream_t st = (hipStream_t)stream;
   char* const out = static_cast<char*>(workspace);

@@ -33,6 +33,7 @@
 #include "bf16x3.h"
 #include "common.h"
 #include "device_math.h"
+#include "entry_args.h"
 #include "siren_chain.h"
 
 namespace mri {
@@ -805,12 +806,22 @@ __global__ __launch_bounds__(kThreads) void rff_wgrad0_kernel(const RffWgradArgs
 }
 
 // ------------------------------------------------------------------------------------------------------ host side
-bool rff_supported(int dim_in, int hidden, int n_freq, int n_layers, int dim_out) {
-  return (hidden == 64 || hidden == 128) && n_freq == hidden && dim_in >= 1 && dim_in <= kFwdIn && n_layers >= 2 &&
-         n_layers <= kMaxSine && dim_out == 1;
+// the fused chains' shape rule (inference, coordinate gradient, training), each argument refused by name
+int check_rff_shape(const char* what, int dim_in, int hidden, int n_freq, int n_layers, int dim_out) {
+  MRI_REQUIRE(hidden == 64 || hidden == 128, "%s: hidden = %d is not supported (64 / 128)", what, hidden);
+  MRI_REQUIRE(n_freq == hidden, "%s: n_freq = %d is not supported (n_freq == hidden = %d)", what, n_freq, hidden);
+  MRI_REQUIRE(dim_in >= 1 && dim_in <= kFwdIn, "%s: dim_in = %d is not supported (1 .. %d)", what, dim_in, kFwdIn);
+  MRI_REQUIRE(n_layers >= 2 && n_layers <= kMaxSine, "%s: n_layers = %d is not supported (2 .. %d)", what, n_layers,
+              kMaxSine);
+  MRI_REQUIRE(dim_out == 1, "%s: dim_out = %d is not supported (1)", what, dim_out);
+  return MRI_OK;
 }
-template <class S>
-int rff_blocks(int64_t n) { return (int)std::min<int64_t>(ceil_div(n, S::rows), 256); }  // one workgroup per CU
+bool rff_supported(int dim_in, int hidden, int n_freq, int n_layers, int dim_out) {
+  return check_rff_shape("fused RFF chain", dim_in, hidden, n_freq, n_layers, dim_out) == MRI_OK;
+}
+int rff_blocks(int hidden, int64_t n) {
+  return persistent_blocks(n, hidden == 128 ? RShape<128>::rows : RShape<64>::rows);
+}
 // the two halves of the first Linear and the n_layers - 2 square ones
 int64_t rff_split_bytes(int hidden, int n_layers) { return (int64_t)n_layers * split_matrix_bytes(hidden); }
 // ... into `out`: Linear 0 is (H, 2F), its cos half starts at column 0, its sin half at column F, both with row stride 2F
@@ -822,22 +833,17 @@ int split_forward_weights(const float* const* weight, int hidden, int n_freq, in
 }
 template <class S>
 int launch_rff_gradient(const RffGradArgs& a, hipStream_t st) {
-  const int blocks = (int)std::min<int64_t>(ceil_div(a.n, S::points), 256);  // one workgroup per CU
-  hipLaunchKernelGGL((rff_gradient_kernel<S>), dim3(blocks), dim3(kThreads), 0, st, a);
+  hipLaunchKernelGGL((rff_gradient_kernel<S>), dim3(persistent_blocks(a.n, S::points)), dim3(kThreads), 0, st, a);
   return check_launch("rff_gradient_kernel");
 }
 
 int check_encode(const float* x, int64_t n, int dim_in, const float* b, int n_freq) {
   MRI_REQUIRE(dim_in >= 1 && dim_in <= kEncIn, "RFF encoding: dim_in = %d is not supported (1 .. %d)", dim_in, kEncIn);
   MRI_REQUIRE(n_freq >= 1, "RFF encoding: n_freq = %d is not supported (>= 1)", n_freq);
-  MRI_REQUIRE(n >= 0 && n < (1ll << 31), "n = %lld out of range", (long long)n);
+  MRI_CHECK(check_rows(n));
   MRI_REQUIRE(n * n_freq < (1ll << 38), "n * n_freq = %lld out of range (one launch)", (long long)(n * n_freq));
   if (n == 0) return MRI_OK;
-  MRI_REQUIRE(x, "x is NULL");
-  MRI_REQUIRE(b, "b is NULL");
-  MRI_REQUIRE(aligned_to(x, 4), "x must be 4-byte aligned");
-  MRI_REQUIRE(aligned_to(b, 4), "b must be 4-byte aligned");
-  return MRI_OK;
+  return check_buffers({{"x", x}, {"b", b}}, 4);
 }
 
 }  // namespace
@@ -847,10 +853,9 @@ using namespace mri;
 
 extern "C" int mri_rff_encode(const float* x, int64_t n, int32_t dim_in, const float* b, int32_t n_freq, float* z,
                               void* stream) {
-  if (int rc = check_encode(x, n, dim_in, b, n_freq)) return rc;
+  MRI_CHECK(check_encode(x, n, dim_in, b, n_freq));
   if (n == 0) return MRI_OK;
-  MRI_REQUIRE(z, "z is NULL");
-  MRI_REQUIRE(aligned_to(z, 4), "z must be 4-byte aligned");
+  MRI_CHECK(check_buffer("z", z, 4));
   hipLaunchKernelGGL(rff_encode_kernel, dim3((unsigned)ceil_div(n * n_freq, 256)), dim3(256), 0, (hipStream_t)stream,
                      x, n, dim_in, b, n_freq, z);
   return check_launch("rff_encode_kernel");
@@ -858,12 +863,9 @@ extern "C" int mri_rff_encode(const float* x, int64_t n, int32_t dim_in, const f
 
 extern "C" int mri_rff_encode_backward_input(const float* x, int64_t n, int32_t dim_in, const float* b,
                                              int32_t n_freq, const float* dz, float* dx, void* stream) {
-  if (int rc = check_encode(x, n, dim_in, b, n_freq)) return rc;
+  MRI_CHECK(check_encode(x, n, dim_in, b, n_freq));
   if (n == 0) return MRI_OK;
-  MRI_REQUIRE(dz, "dz is NULL");
-  MRI_REQUIRE(dx, "dx is NULL");
-  MRI_REQUIRE(aligned_to(dz, 4), "dz must be 4-byte aligned");
-  MRI_REQUIRE(aligned_to(dx, 4), "dx must be 4-byte aligned");
+  MRI_CHECK(check_buffers({{"dz", dz}, {"dx", dx}}, 4));
   hipLaunchKernelGGL(rff_encode_backward_kernel, dim3((unsigned)ceil_div(n, 4)), dim3(256), 0, (hipStream_t)stream, x,
                      n, dim_in, b, n_freq, dz, dx);
   return check_launch("rff_encode_backward_kernel");
@@ -883,44 +885,25 @@ extern "C" int mri_rff_forward(const float* x, int64_t n, int32_t dim_in, int32_
                                int32_t n_layers, const float* b, const float* const* weight,
                                const float* const* bias, float* y, void* workspace, int64_t workspace_bytes,
                                void* stream) {
-  MRI_REQUIRE(hidden == 64 || hidden == 128, "fused RFF forward: hidden = %d is not supported (64 / 128)", hidden);
-  MRI_REQUIRE(n_freq == hidden, "fused RFF forward: n_freq = %d is not supported (n_freq == hidden = %d)", n_freq,
-              hidden);
-  MRI_REQUIRE(dim_in >= 1 && dim_in <= kFwdIn, "fused RFF forward: dim_in = %d is not supported (1 .. %d)", dim_in,
-              kFwdIn);
-  MRI_REQUIRE(n_layers >= 2 && n_layers <= kMaxSine, "fused RFF forward: n_layers = %d is not supported (2 .. %d)",
-              n_layers, kMaxSine);
-  MRI_REQUIRE(rff_supported(dim_in, hidden, n_freq, n_layers, 1), "fused RFF forward: %d -> %d x %d -> 1 is not supported",
-              dim_in, hidden, n_layers);
-  MRI_REQUIRE(n >= 0 && n < (1ll << 31), "n = %lld out of range", (long long)n);
+  const char* const what = "fused RFF forward";
+  MRI_CHECK(check_rff_shape(what, dim_in, hidden, n_freq, n_layers, 1));
+  MRI_CHECK(check_rows(n));
   if (n == 0) return MRI_OK;
-  MRI_REQUIRE(x, "x is NULL");
-  MRI_REQUIRE(b, "b is NULL");
-  MRI_REQUIRE(y, "y is NULL");
-  MRI_REQUIRE(weight, "weight is NULL");
-  MRI_REQUIRE(bias, "bias is NULL");
-  MRI_REQUIRE(aligned_to(x, 4), "x must be 4-byte aligned");
-  MRI_REQUIRE(aligned_to(b, 4), "b must be 4-byte aligned");
-  MRI_REQUIRE(aligned_to(y, 4), "y must be 4-byte aligned");
-  const int64_t need = rff_split_bytes(hidden, n_layers);
-  MRI_REQUIRE(workspace && workspace_bytes >= need && aligned_to(workspace, 16),
-              "workspace: the fused RFF forward needs %lld bytes, 16-byte aligned (mri_rff_forward_workspace_bytes)",
-              (long long)need);
+  MRI_CHECK(check_buffers({{"x", x}, {"b", b}, {"y", y}}, 4));
+  MRI_CHECK(check_buffers({{"weight", weight}, {"bias", bias}}, kAnyAlignment));
+  MRI_CHECK(check_workspace(what, "mri_rff_forward_workspace_bytes", workspace, workspace_bytes,
+                            rff_split_bytes(hidden, n_layers)));
+  MRI_CHECK(check_pointers({{"weight", weight}, {"bias", bias}}, 0, n_layers, 4));
   RffArgs a{};
   a.x = x, a.n = n, a.dim_in = dim_in, a.L = n_layers, a.b = b, a.y = y;
-  for (int l = 0; l < n_layers; ++l) {
-    MRI_REQUIRE(weight[l], "weight[%d] is NULL", l);
-    MRI_REQUIRE(bias[l], "bias[%d] is NULL", l);
-    MRI_REQUIRE(aligned_to(weight[l], 4) && aligned_to(bias[l], 4), "weight[%d] / bias[%d] must be 4-byte aligned", l, l);
-    a.bias[l] = bias[l];
-  }
+  std::copy(bias, bias + n_layers, a.bias);
   a.w_head = weight[n_layers - 1];
   a.wsplit = static_cast<const char*>(workspace);
   hipStream_t st = (hipStream_t)stream;
   if (int rc = split_forward_weights(weight, hidden, n_freq, n_layers, static_cast<char*>(workspace), st)) return rc;
   return dispatch_hidden_mod(hidden, [&](auto h) {
     using S = RShape<decltype(h)::value>;
-    hipLaunchKernelGGL((rff_forward_kernel<false, S>), dim3(rff_blocks<S>(n)), dim3(kThreads), 0, st, a);
+    hipLaunchKernelGGL((rff_forward_kernel<false, S>), dim3(rff_blocks(hidden, n)), dim3(kThreads), 0, st, a);
     return check_launch("rff_forward_kernel");
   });
 }
@@ -939,31 +922,18 @@ extern "C" int mri_rff_gradient(const float* x, int64_t n, int32_t dim_in, int32
                                 int32_t n_layers, const float* b, const float* const* weight,
                                 const float* const* bias, float* y, float* dydx, void* workspace,
                                 int64_t workspace_bytes, void* stream) {
-  MRI_REQUIRE(hidden == 64 || hidden == 128, "fused RFF gradient: hidden = %d is not supported (64 / 128)", hidden);
-  MRI_REQUIRE(n_freq == hidden, "fused RFF gradient: n_freq = %d is not supported (n_freq == hidden = %d)", n_freq,
-              hidden);
-  MRI_REQUIRE(dim_in >= 1 && dim_in <= kFwdIn, "fused RFF gradient: dim_in = %d is not supported (1 .. %d)", dim_in,
-              kFwdIn);
-  MRI_REQUIRE(n_layers >= 2 && n_layers <= kMaxSine, "fused RFF gradient: n_layers = %d is not supported (2 .. %d)",
-              n_layers, kMaxSine);
-  if (int rc = check_gradient_io(x, n, y, dydx)) return rc;
+  const char* const what = "fused RFF gradient";
+  MRI_CHECK(check_rff_shape(what, dim_in, hidden, n_freq, n_layers, 1));
+  MRI_CHECK(check_gradient_io(x, n, y, dydx));
   if (n == 0) return MRI_OK;
-  MRI_REQUIRE(b, "b is NULL");
-  MRI_REQUIRE(weight, "weight is NULL");
-  MRI_REQUIRE(bias, "bias is NULL");
-  MRI_REQUIRE(aligned_to(b, 4), "b must be 4-byte aligned");
-  const int64_t need = rff_split_bytes(hidden, n_layers);
-  MRI_REQUIRE(workspace && workspace_bytes >= need && aligned_to(workspace, 16),
-              "workspace: the fused RFF gradient needs %lld bytes, 16-byte aligned (mri_rff_gradient_workspace_bytes)",
-              (long long)need);
+  MRI_CHECK(check_buffer("b", b, 4));
+  MRI_CHECK(check_buffers({{"weight", weight}, {"bias", bias}}, kAnyAlignment));
+  MRI_CHECK(check_workspace(what, "mri_rff_gradient_workspace_bytes", workspace, workspace_bytes,
+                            rff_split_bytes(hidden, n_layers)));
+  MRI_CHECK(check_pointers({{"weight", weight}, {"bias", bias}}, 0, n_layers, 4));
   RffGradArgs a{};
   a.x = x, a.n = n, a.dim_in = dim_in, a.L = n_layers, a.b = b, a.y = y, a.dydx = dydx;
-  for (int l = 0; l < n_layers; ++l) {
-    MRI_REQUIRE(weight[l], "weight[%d] is NULL", l);
-    MRI_REQUIRE(bias[l], "bias[%d] is NULL", l);
-    MRI_REQUIRE(aligned_to(weight[l], 4) && aligned_to(bias[l], 4), "weight[%d] / bias[%d] must be 4-byte aligned", l, l);
-    a.bias[l] = bias[l];
-  }
+  std::copy(bias, bias + n_layers, a.bias);
   a.w_head = weight[n_layers - 1];
   a.wsplit = static_cast<const char*>(workspace);
   hipStream_t st = (hipStream_t)stream;
@@ -979,11 +949,8 @@ namespace mri {
 namespace {
 
 // workspace of the two training calls: [slabs of partial sums][forward splits: n_layers][transposed splits: n_layers - 2]
-int rff_blocks_of(int hidden, int64_t n) {
-  return hidden == 128 ? rff_blocks<RShape<128>>(n) : rff_blocks<RShape<64>>(n);
-}
 int64_t rff_slab_bytes(int64_t n, int hidden, int L) {
-  const int64_t blocks = rff_blocks_of(hidden, n);
+  const int64_t blocks = rff_blocks(hidden, n);
   // the chain kernel's slabs (the forward's loss shares fit inside), the square weight gradients' and dW_0's two halves
   const int64_t chain = std::max<int64_t>(blocks * RffBwdSlab{hidden, L}.floats(), 256);
   const int64_t bytes = std::max(chain, 2 * wgrad_slab_floats(n, hidden)) * 4;
@@ -991,24 +958,6 @@ int64_t rff_slab_bytes(int64_t n, int hidden, int L) {
 }
 int64_t rff_train_bytes(int64_t n, int hidden, int L) {
   return rff_slab_bytes(n, hidden, L) + (int64_t)(2 * L - 2) * split_matrix_bytes(hidden);
-}
-
-// the shape arguments of the training entry points, each refused by name
-int check_train_shape(const char* what, int dim_in, int hidden, int n_freq, int n_layers) {
-  MRI_REQUIRE(hidden == 64 || hidden == 128, "%s: hidden = %d is not supported (64 / 128)", what, hidden);
-  MRI_REQUIRE(n_freq == hidden, "%s: n_freq = %d is not supported (n_freq == hidden = %d)", what, n_freq, hidden);
-  MRI_REQUIRE(dim_in >= 1 && dim_in <= kFwdIn, "%s: dim_in = %d is not supported (1 .. %d)", what, dim_in, kFwdIn);
-  MRI_REQUIRE(n_layers >= 2 && n_layers <= kMaxSine, "%s: n_layers = %d is not supported (2 .. %d)", what, n_layers,
-              kMaxSine);
-  return MRI_OK;
-}
-
-int check_train_workspace(const char* what, const void* workspace, int64_t workspace_bytes, int64_t need) {
-  MRI_REQUIRE(workspace, "%s: workspace is NULL (%lld bytes, mri_rff_backward_workspace_bytes)", what, (long long)need);
-  MRI_REQUIRE(workspace_bytes >= need, "%s: workspace of %lld bytes is short of %lld (mri_rff_backward_workspace_bytes)",
-              what, (long long)workspace_bytes, (long long)need);
-  MRI_REQUIRE(aligned_to(workspace, 16), "%s: workspace must be 16-byte aligned", what);
-  return MRI_OK;
 }
 
 }  // namespace
@@ -1030,39 +979,21 @@ extern "C" int mri_rff_forward_loss(const float* x, const float* target, int64_t
                                     float* const* act, float* y, float* dy, float* loss_out, void* workspace,
                                     int64_t workspace_bytes, void* stream) {
   const char* const what = "fused RFF forward with loss";
-  if (int rc = check_train_shape(what, dim_in, hidden, n_freq, n_layers)) return rc;
-  MRI_REQUIRE(n >= 0 && n < (1ll << 31), "n = %lld out of range", (long long)n);
-  MRI_REQUIRE(n_total >= n, "n_total = %lld is less than n = %lld (n is a slice of the batch)", (long long)n_total,
-              (long long)n);
-  MRI_REQUIRE(grad_divisor > 0.f, "grad_divisor = %g is not positive", (double)grad_divisor);
+  MRI_CHECK(check_rff_shape(what, dim_in, hidden, n_freq, n_layers, 1));
+  MRI_CHECK(check_batch_slice(n, n_total, grad_divisor));
   if (n == 0) return MRI_OK;
-  MRI_REQUIRE(x, "x is NULL");
-  MRI_REQUIRE(target, "target is NULL");
-  MRI_REQUIRE(b, "b is NULL");
-  MRI_REQUIRE(weight, "weight is NULL");
-  MRI_REQUIRE(bias, "bias is NULL");
-  MRI_REQUIRE(act, "act is NULL");
-  MRI_REQUIRE(y, "y is NULL");
-  MRI_REQUIRE(dy, "dy is NULL");
-  MRI_REQUIRE(loss_out, "loss_out is NULL");
-  MRI_REQUIRE(aligned_to(x, 4) && aligned_to(target, 4) && aligned_to(b, 4) && aligned_to(y, 4) && aligned_to(dy, 4) &&
-                  aligned_to(loss_out, 4), "x / target / b / y / dy / loss_out must be 4-byte aligned");
+  MRI_CHECK(check_buffers({{"x", x}, {"target", target}, {"b", b}}, 4));
+  MRI_CHECK(check_buffers({{"weight", weight}, {"bias", bias}, {"act", act}}, kAnyAlignment));
+  MRI_CHECK(check_buffers({{"y", y}, {"dy", dy}, {"loss_out", loss_out}}, 4));
+  MRI_CHECK(check_pointers({{"weight", weight}, {"bias", bias}}, 0, n_layers, 4));
+  // (the weight-gradient kernels stream act in 16-byte pieces)
+  MRI_CHECK(check_pointers({{"act", act}}, 0, n_layers - 1, 16));
+  MRI_CHECK(check_workspace(what, "mri_rff_backward_workspace_bytes", workspace, workspace_bytes,
+                            rff_train_bytes(n, hidden, n_layers)));
   RffArgs a{};
   a.x = x, a.n = n, a.dim_in = dim_in, a.L = n_layers, a.b = b, a.y = y;
-  for (int l = 0; l < n_layers; ++l) {
-    MRI_REQUIRE(weight[l], "weight[%d] is NULL", l);
-    MRI_REQUIRE(bias[l], "bias[%d] is NULL", l);
-    MRI_REQUIRE(aligned_to(weight[l], 4) && aligned_to(bias[l], 4), "weight[%d] / bias[%d] must be 4-byte aligned", l, l);
-    a.bias[l] = bias[l];
-  }
-  for (int l = 0; l + 1 < n_layers; ++l) {
-    MRI_REQUIRE(act[l], "act[%d] is NULL", l);
-    // (the weight-gradient kernels stream them in 16-byte pieces)
-    MRI_REQUIRE(aligned_to(act[l], 16), "act[%d] must be 16-byte aligned", l);
-    a.act[l] = act[l];
-  }
-  const int64_t need = rff_train_bytes(n, hidden, n_layers);
-  if (int rc = check_train_workspace(what, workspace, workspace_bytes, need)) return rc;
+  std::copy(bias, bias + n_layers, a.bias);
+  std::copy(act, act + n_layers - 1, a.act);
   char* const wsplit = static_cast<char*>(workspace) + rff_slab_bytes(n, hidden, n_layers);
   a.w_head = weight[n_layers - 1], a.wsplit = wsplit;
   a.target = target, a.dy_out = dy, a.partial = static_cast<float*>(workspace);
@@ -1070,7 +1001,7 @@ extern "C" int mri_rff_forward_loss(const float* x, const float* target, int64_t
   a.inv_n = (float)(1.0 / (double)n_total);
   hipStream_t st = (hipStream_t)stream;
   if (int rc = split_forward_weights(weight, hidden, n_freq, n_layers, wsplit, st)) return rc;
-  const int blocks = rff_blocks_of(hidden, n);
+  const int blocks = rff_blocks(hidden, n);
   if (int rc = dispatch_hidden_mod(hidden, [&](auto h) {
         using S = RShape<decltype(h)::value>;
         hipLaunchKernelGGL((rff_forward_kernel<true, S>), dim3(blocks), dim3(kThreads), 0, st, a);
@@ -1087,37 +1018,21 @@ extern "C" int mri_rff_backward(const float* x, const float* dy, int64_t n, int3
                                 const float* const* act, float* const* dz, float* const* d_weight,
                                 float* const* d_bias, void* workspace, int64_t workspace_bytes, void* stream) {
   const char* const what = "fused RFF backward";
-  if (int rc = check_train_shape(what, dim_in, hidden, n_freq, n_layers)) return rc;
-  MRI_REQUIRE(n >= 0 && n < (1ll << 31), "n = %lld out of range", (long long)n);
+  MRI_CHECK(check_rff_shape(what, dim_in, hidden, n_freq, n_layers, 1));
+  MRI_CHECK(check_rows(n));
   if (n == 0) return MRI_OK;
-  MRI_REQUIRE(x, "x is NULL");
-  MRI_REQUIRE(dy, "dy is NULL");
-  MRI_REQUIRE(b, "b is NULL");
-  MRI_REQUIRE(weight, "weight is NULL");
-  MRI_REQUIRE(act, "act is NULL");
-  MRI_REQUIRE(dz, "dz is NULL");
-  MRI_REQUIRE(d_weight, "d_weight is NULL");
-  MRI_REQUIRE(d_bias, "d_bias is NULL");
-  MRI_REQUIRE(aligned_to(x, 4) && aligned_to(dy, 4) && aligned_to(b, 4), "x / dy / b must be 4-byte aligned");
   const int L = n_layers;
+  MRI_CHECK(check_buffers({{"x", x}, {"dy", dy}, {"b", b}}, 4));
+  MRI_CHECK(check_buffers({{"weight", weight}, {"act", act}, {"dz", dz}, {"d_weight", d_weight}, {"d_bias", d_bias}},
+                          kAnyAlignment));
+  MRI_CHECK(check_pointers({{"weight", weight}, {"d_weight", d_weight}, {"d_bias", d_bias}}, 0, L, 4));
+  MRI_CHECK(check_pointers({{"act", act}, {"dz", dz}}, 0, L - 1, 16));
+  MRI_CHECK(check_workspace(what, "mri_rff_backward_workspace_bytes", workspace, workspace_bytes,
+                            rff_train_bytes(n, hidden, L)));
   RffBwdArgs a{};
   a.dy = dy, a.n = n, a.L = L;
-  for (int l = 0; l < L; ++l) {
-    MRI_REQUIRE(weight[l], "weight[%d] is NULL", l);
-    MRI_REQUIRE(d_weight[l], "d_weight[%d] is NULL", l);
-    MRI_REQUIRE(d_bias[l], "d_bias[%d] is NULL", l);
-    MRI_REQUIRE(aligned_to(weight[l], 4) && aligned_to(d_weight[l], 4) && aligned_to(d_bias[l], 4),
-                "weight[%d] / d_weight[%d] / d_bias[%d] must be 4-byte aligned", l, l, l);
-  }
-  for (int l = 0; l + 1 < L; ++l) {
-    MRI_REQUIRE(act[l], "act[%d] is NULL", l);
-    MRI_REQUIRE(dz[l], "dz[%d] is NULL", l);
-    MRI_REQUIRE(aligned_to(act[l], 16), "act[%d] must be 16-byte aligned", l);
-    MRI_REQUIRE(aligned_to(dz[l], 16), "dz[%d] must be 16-byte aligned", l);
-    a.act[l] = act[l], a.dz[l] = dz[l];
-  }
-  const int64_t need = rff_train_bytes(n, hidden, L);
-  if (int rc = check_train_workspace(what, workspace, workspace_bytes, need)) return rc;
+  std::copy(act, act + L - 1, a.act);
+  std::copy(dz, dz + L - 1, a.dz);
   a.w_head = weight[L - 1];
   a.partial = static_cast<float*>(workspace);
   const int64_t smb = split_matrix_bytes(hidden);
@@ -1125,7 +1040,7 @@ extern "C" int mri_rff_backward(const float* x, const float* dy, int64_t n, int3
   a.wtsplit = wtsplit;
   hipStream_t st = (hipStream_t)stream;
   if (int rc = split_weights_ld(weight + 1, L - 2, hidden, hidden, true, wtsplit, smb, st)) return rc;
-  const int blocks = rff_blocks_of(hidden, n);
+  const int blocks = rff_blocks(hidden, n);
   if (int rc = dispatch_hidden_mod(hidden, [&](auto h) {
         using S = RShape<decltype(h)::value>;
         hipLaunchKernelGGL((rff_backward_kernel<S>), dim3(blocks), dim3(kThreads), 0, st, a);

@@ -1,7 +1,8 @@
 // Declarations shared by the two families of fused SIREN chain kernels: siren_chain.hip (the activation image of a
 // row tile in LDS, every width) and siren_rows.hip (H = 256: the activations of a wave's rows in registers).
 // modsiren.hip (ModulatedSirenNet: two images per row tile) and the two coordinate-gradient files share the weight-split /
-// weight-gradient launches of siren_chain.hip.  The device side of the LDS-image tile loop is chain_tile.h.
+// weight-gradient launches of siren_chain.hip.  The device side of the LDS-image tile loop is chain_tile.h; what the
+// entry points ask of their arguments (check_gradient_io among it) is entry_args.h.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -103,19 +104,6 @@ int dispatch_hidden(int hidden, F&& f) {
 template <class F>
 int dispatch_hidden_mod(int hidden, F&& f) {
   return hidden == 128 ? f(std::integral_constant<int, 128>{}) : f(std::integral_constant<int, 64>{});
-}
-
-// what the two coordinate-gradient entry points ask of n, x, y and dydx (n = 0 passes: the caller returns then)
-inline int check_gradient_io(const float* x, int64_t n, const float* y, const float* dydx) {
-  MRI_REQUIRE(n >= 0 && n < (1ll << 31), "n = %lld out of range", (long long)n);
-  if (n == 0) return MRI_OK;
-  MRI_REQUIRE(x, "x is NULL");
-  MRI_REQUIRE(y, "y is NULL");
-  MRI_REQUIRE(dydx, "dydx is NULL");
-  MRI_REQUIRE(aligned_to(x, 4), "x must be 4-byte aligned");
-  MRI_REQUIRE(aligned_to(y, 4), "y must be 4-byte aligned");
-  MRI_REQUIRE(aligned_to(dydx, 4), "dydx must be 4-byte aligned");
-  return MRI_OK;
 }
 
 }  // namespace mri

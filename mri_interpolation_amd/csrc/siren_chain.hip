@@ -27,6 +27,7 @@
 #include "bf16x3.h"
 #include "common.h"
 #include "device_math.h"
+#include "entry_args.h"
 #include "siren_chain.h"
 
 // The H x H products run on the bf16 matrix pipe, f32-accurate (bf16x3.h): every operand is split
@@ -808,13 +809,19 @@ int64_t split_region_bytes(int hidden, int n_sine) {
 int64_t slab_region_bytes(int64_t n, int hidden, int n_sine);
 
 // ------------------------------------------------------------------------------ host side
+int check_chain_shape(const char* what, int dim_in, int hidden, int n_sine, int dim_out) {
+  MRI_REQUIRE((hidden == 32 || hidden == 64 || hidden == 128 || hidden == 256) && dim_in >= 1 && dim_in <= kMaxIn &&
+                  n_sine >= 1 && n_sine <= kMaxSine && dim_out == 1,
+              "%s: %d -> %d x %d -> %d is not supported (hidden 32 / 64 / 128 / 256, dim_in <= 8, <= %d sine layers)",
+              what, dim_in, hidden, n_sine, dim_out, kMaxSine);
+  return MRI_OK;
+}
 bool chain_supported(int dim_in, int hidden, int n_sine, int dim_out) {
-  return (hidden == 32 || hidden == 64 || hidden == 128 || hidden == 256) && dim_in >= 1 &&
-         dim_in <= kMaxIn && n_sine >= 1 && n_sine <= kMaxSine && dim_out == 1;
+  return check_chain_shape("fused SIREN chain", dim_in, hidden, n_sine, dim_out) == MRI_OK;
 }
 
 int tile_rows(int hidden) { return hidden >= 256 ? 64 : hidden == 128 ? 128 : 256; }
-int chain_blocks(int hidden, int64_t n) { return (int)std::min<int64_t>(ceil_div(n, tile_rows(hidden)), 256); }
+int chain_blocks(int hidden, int64_t n) { return persistent_blocks(n, tile_rows(hidden)); }
 
 template <int H>
 int launch_forward(const ChainArgs& a, int mode, hipStream_t st) {
@@ -879,7 +886,7 @@ int wgrad_any_ld(int hidden, const WgradArgs& g, float* d_weight, int ld, hipStr
 }
 
 int wgrad_split(int hidden) { return hidden >= 128 ? 1 : hidden == 64 ? 2 : 8; }
-int wgrad_blocks(int64_t n) { return (int)std::min<int64_t>(ceil_div(n, kWr), 256); }
+int wgrad_blocks(int64_t n) { return persistent_blocks(n, kWr); }
 int sum_wgrad_slabs(const float* partial, int slabs, int count, const SlabDest& to, hipStream_t st) {
   hipLaunchKernelGGL(slab_sum_kernel, dim3((unsigned)ceil_div(count, 256)), dim3(256), 0, st, partial, slabs, count, to);
   return check_launch("slab_sum_kernel");
@@ -894,9 +901,16 @@ int64_t wgrad_slab_floats(int64_t n, int hidden) {
 using namespace mri;
 
 namespace {
+// the n_sine + 1 Linears of a forward call (the operand split reads the weights in 16-byte pieces)
+int check_parameters(const float* const* weight, const float* const* bias, int n_sine) {
+  MRI_CHECK(check_pointers({{"weight", weight}}, 0, n_sine + 1, 16));
+  return check_pointers({{"bias", bias}}, 0, n_sine + 1, kAnyAlignment);
+}
 // The (n, hidden) tensors leave and return in 16-byte pieces: the rows kernels (hidden 256) store act / deriv / dz_last
 // four floats a lane, the weight-gradient kernels stream act and dz into LDS sixteen bytes a lane.
-constexpr const char* kActAlignment = "act / deriv buffers must be 16-byte aligned (layer %d)";
+int check_saved(const void* act, const void* deriv, int count) {
+  return check_pointers({{"act", act}, {"deriv", deriv}}, 0, count, 16);
+}
 }  // namespace
 
 extern "C" int mri_siren_supported(int32_t dim_in, int32_t hidden, int32_t n_sine_layers,
@@ -909,33 +923,24 @@ extern "C" int mri_siren_forward(const float* x, int64_t n, int32_t dim_in, int3
                                  const float* const* bias, float w0_first, float w0,
                                  float* const* act, float* const* deriv, float* y, void* workspace,
                                  int64_t workspace_bytes, void* stream) {
-  MRI_REQUIRE(chain_supported(dim_in, hidden, n_sine_layers, 1),
-              "fused SIREN chain: %d -> %d x %d -> 1 is not supported (hidden 32 / 64 / 128 / 256, "
-              "dim_in <= 8, <= %d sine layers)", dim_in, hidden, n_sine_layers, kMaxSine);
-  MRI_REQUIRE(n >= 0 && n < (1ll << 31), "n = %lld out of range", (long long)n);
+  MRI_CHECK(check_chain_shape("fused SIREN chain", dim_in, hidden, n_sine_layers, 1));
+  MRI_CHECK(check_rows(n));
   if (n == 0) return MRI_OK;
-  MRI_REQUIRE(x && weight && bias && y, "NULL pointer");
-  const int64_t need = split_region_bytes(hidden, n_sine_layers);
-  MRI_REQUIRE(need == 0 || (workspace && workspace_bytes >= need &&
-                            aligned_to(workspace, 16)),
-              "SIREN forward needs a 16-byte aligned workspace of %lld bytes "
-              "(mri_siren_forward_workspace_bytes)", (long long)need);
+  MRI_CHECK(check_buffers({{"x", x}, {"weight", weight}, {"bias", bias}, {"y", y}}, kAnyAlignment));
+  MRI_CHECK(check_workspace("SIREN forward", "mri_siren_forward_workspace_bytes", workspace, workspace_bytes,
+                            split_region_bytes(hidden, n_sine_layers)));
   MRI_REQUIRE((act == nullptr) == (deriv == nullptr), "act and deriv go together");
+  MRI_CHECK(check_parameters(weight, bias, n_sine_layers));
   ChainArgs a{};
   a.x = x, a.n = n, a.dim_in = dim_in, a.n_sine = n_sine_layers;
   a.w0_first = w0_first, a.w0 = w0, a.y = y;
-  for (int l = 0; l <= n_sine_layers; ++l) {
-    MRI_REQUIRE(weight[l] && bias[l], "NULL parameter pointer (layer %d)", l);
-    MRI_REQUIRE(aligned_to(weight[l], 16),
-                "weights must be 16-byte aligned (layer %d)", l);
-    a.w[l] = weight[l], a.b[l] = bias[l];
+  std::copy(weight, weight + n_sine_layers + 1, a.w);
+  std::copy(bias, bias + n_sine_layers + 1, a.b);
+  if (act) {
+    MRI_CHECK(check_saved(act, deriv, n_sine_layers));
+    std::copy(act, act + n_sine_layers, a.act);
+    std::copy(deriv, deriv + n_sine_layers, a.deriv);
   }
-  if (act)
-    for (int l = 0; l < n_sine_layers; ++l) {
-      MRI_REQUIRE(act[l] && deriv[l], "NULL activation buffer (layer %d)", l);
-      MRI_REQUIRE(aligned_to(act[l], 16) && aligned_to(deriv[l], 16), kActAlignment, l);
-      a.act[l] = act[l], a.deriv[l] = deriv[l];
-    }
   a.wsplit = static_cast<const char*>(workspace);
   if (int rc = split_weights(weight, n_sine_layers, hidden, false, static_cast<char*>(workspace),
                              (hipStream_t)stream))
@@ -986,18 +991,21 @@ extern "C" int mri_siren_forward_loss(const float* x, const float* target, int64
                                       float* dz_last, float* y, float* d_w_head, float* d_b_head,
                                       float* d_b_last, float* loss_out, void* workspace,
                                       int64_t workspace_bytes, void* stream) {
-  MRI_REQUIRE(chain_supported(dim_in, hidden, n_sine_layers, 1) && n_sine_layers >= 2,
-              "fused SIREN chain with loss: %d -> %d x %d -> 1 is not supported (>= 2 sine layers)",
-              dim_in, hidden, n_sine_layers);
-  MRI_REQUIRE(n >= 0 && n < (1ll << 31) && n_total >= n && grad_divisor > 0.f, "bad n / divisor");
+  const char* const what = "fused SIREN chain with loss";
+  MRI_CHECK(check_chain_shape(what, dim_in, hidden, n_sine_layers, 1));
+  MRI_REQUIRE(n_sine_layers >= 2, "%s: %d -> %d x %d -> 1 is not supported (>= 2 sine layers)", what, dim_in, hidden,
+              n_sine_layers);
+  MRI_CHECK(check_batch_slice(n, n_total, grad_divisor));
   if (n == 0) return MRI_OK;
-  MRI_REQUIRE(x && target && weight && bias && act && deriv && dz_last && y && d_w_head &&
-                  d_b_head && d_b_last && loss_out, "NULL pointer");
+  MRI_CHECK(check_buffers({{"x", x}, {"target", target}, {"weight", weight}, {"bias", bias}, {"act", act},
+                           {"deriv", deriv}, {"dz_last", dz_last}, {"y", y}, {"d_w_head", d_w_head},
+                           {"d_b_head", d_b_head}, {"d_b_last", d_b_last}, {"loss_out", loss_out}}, kAnyAlignment));
   const int blocks = chain_blocks(hidden, n);
-  const int64_t need = mri_siren_backward_workspace_bytes(n, hidden, n_sine_layers);
-  MRI_REQUIRE(workspace && workspace_bytes >= need && aligned_to(workspace, 16),
-              "SIREN forward with loss needs a 16-byte aligned workspace of %lld bytes "
-              "(mri_siren_backward_workspace_bytes)", (long long)need);
+  MRI_CHECK(check_workspace("SIREN forward with loss", "mri_siren_backward_workspace_bytes", workspace, workspace_bytes,
+                            mri_siren_backward_workspace_bytes(n, hidden, n_sine_layers)));
+  MRI_CHECK(check_parameters(weight, bias, n_sine_layers));
+  MRI_CHECK(check_saved(act, deriv, n_sine_layers - 1));  // the last sine layer's a / w0 cos stay on chip
+  MRI_CHECK(check_buffer("dz_last", dz_last, 16));
   char* const wsplit = static_cast<char*>(workspace) + slab_region_bytes(n, hidden, n_sine_layers);
   ChainArgs a{};
   a.x = x, a.n = n, a.dim_in = dim_in, a.n_sine = n_sine_layers;
@@ -1006,18 +1014,10 @@ extern "C" int mri_siren_forward_loss(const float* x, const float* target, int64
   a.dy_ws = reinterpret_cast<float*>(static_cast<char*>(workspace) + rows_dy_offset(n, hidden, n_sine_layers));
   a.grad_scale = (float)(2.0 / ((double)n_total * (double)grad_divisor));
   a.inv_n = (float)(1.0 / (double)n_total);
-  for (int l = 0; l <= n_sine_layers; ++l) {
-    MRI_REQUIRE(weight[l] && bias[l], "NULL parameter pointer (layer %d)", l);
-    MRI_REQUIRE(aligned_to(weight[l], 16),
-                "weights must be 16-byte aligned (layer %d)", l);
-    a.w[l] = weight[l], a.b[l] = bias[l];
-  }
-  for (int l = 0; l + 1 < n_sine_layers; ++l) {  // the last sine layer's a / w0 cos stay on chip
-    MRI_REQUIRE(act[l] && deriv[l], "NULL activation buffer (layer %d)", l);
-    MRI_REQUIRE(aligned_to(act[l], 16) && aligned_to(deriv[l], 16), kActAlignment, l);
-    a.act[l] = act[l], a.deriv[l] = deriv[l];
-  }
-  MRI_REQUIRE(aligned_to(dz_last, 16), "dz_last must be 16-byte aligned");
+  std::copy(weight, weight + n_sine_layers + 1, a.w);
+  std::copy(bias, bias + n_sine_layers + 1, a.b);
+  std::copy(act, act + n_sine_layers - 1, a.act);
+  std::copy(deriv, deriv + n_sine_layers - 1, a.deriv);
   hipStream_t st = (hipStream_t)stream;
   a.wsplit = wsplit;
   remember_loss_call(LossCall{workspace, dz_last, n, hidden, n_sine_layers,
@@ -1055,37 +1055,30 @@ extern "C" int mri_siren_backward(const float* x, const float* dy, int64_t n, in
                                   float* const* d_weight, float* const* d_bias,
                                   int32_t head_done, void* workspace, int64_t workspace_bytes,
                                   void* stream) {
-  MRI_REQUIRE(chain_supported(dim_in, hidden, n_sine_layers, 1),
-              "fused SIREN chain: %d -> %d x %d -> 1 is not supported", dim_in, hidden,
-              n_sine_layers);
+  MRI_CHECK(check_chain_shape("fused SIREN chain", dim_in, hidden, n_sine_layers, 1));
   MRI_REQUIRE(!head_done || n_sine_layers >= 2, "head_done needs >= 2 sine layers");
-  MRI_REQUIRE(n >= 0 && n < (1ll << 31), "n = %lld out of range", (long long)n);
+  MRI_CHECK(check_rows(n));
   if (n == 0) return MRI_OK;
-  MRI_REQUIRE(x && (dy || head_done) && weight && act && deriv && dz && d_weight && d_bias,
-              "NULL pointer");
   const int L = n_sine_layers;
-  const int64_t need = mri_siren_backward_workspace_bytes(n, hidden, L);
-  MRI_REQUIRE(workspace && workspace_bytes >= need && aligned_to(workspace, 16),
-              "SIREN backward needs a 16-byte aligned workspace of %lld bytes "
-              "(mri_siren_backward_workspace_bytes)", (long long)need);
+  MRI_CHECK(check_buffer("x", x, kAnyAlignment));
+  if (!head_done) MRI_CHECK(check_buffer("dy", dy, kAnyAlignment));
+  MRI_CHECK(check_buffers({{"weight", weight}, {"act", act}, {"deriv", deriv}, {"dz", dz}, {"d_weight", d_weight},
+                           {"d_bias", d_bias}}, kAnyAlignment));
+  MRI_CHECK(check_workspace("SIREN backward", "mri_siren_backward_workspace_bytes", workspace, workspace_bytes,
+                            mri_siren_backward_workspace_bytes(n, hidden, L)));
+  MRI_CHECK(check_pointers({{"weight", weight}}, 0, L + 1, 16));
+  MRI_CHECK(check_pointers({{"d_weight", d_weight}, {"d_bias", d_bias}}, 0, L + 1, kAnyAlignment));
+  MRI_CHECK(check_saved(act, deriv, head_done ? L - 1 : L));  // (the loss-mode forward never stored the last layer's)
+  MRI_CHECK(check_pointers({{"dz", dz}}, 1, L - 1, 16));
   hipStream_t st = (hipStream_t)stream;
   char* const wtsplit = static_cast<char*>(workspace) + slab_region_bytes(n, hidden, L);
   BwdArgs a{};
   a.x = x, a.dy = dy, a.n = n, a.dim_in = dim_in, a.n_sine = L;
   a.partial = static_cast<float*>(workspace);
   a.dy_ws = reinterpret_cast<const float*>(static_cast<const char*>(workspace) + rows_dy_offset(n, hidden, L));
-  for (int l = 0; l <= L; ++l) {
-    MRI_REQUIRE(weight[l] && d_weight[l] && d_bias[l], "NULL parameter / gradient pointer (layer %d)", l);
-    MRI_REQUIRE(aligned_to(weight[l], 16), "weights must be 16-byte aligned");
-    a.w[l] = weight[l];
-  }
+  std::copy(weight, weight + L + 1, a.w);
   for (int l = 0; l < L; ++l) {
-    const bool on_chip = head_done && l == L - 1;  // the loss-mode forward never stored these
-    MRI_REQUIRE((on_chip || (act[l] && deriv[l])) && (l == 0 || dz[l]),
-                "NULL activation buffer (layer %d)", l);
-    MRI_REQUIRE(on_chip || (aligned_to(act[l], 16) && aligned_to(deriv[l], 16)), kActAlignment, l);
-    MRI_REQUIRE(l == 0 || aligned_to(dz[l], 16), "dz buffers must be 16-byte aligned (layer %d)", l);
-    a.deriv[l] = on_chip ? nullptr : deriv[l];
+    a.deriv[l] = head_done && l == L - 1 ? nullptr : deriv[l];
     a.dz[l] = dz[l];
   }
   a.act_last = head_done ? nullptr : act[L - 1];

@@ -31,6 +31,7 @@
 #include "bf16x3.h"
 #include "common.h"
 #include "device_math.h"
+#include "entry_args.h"
 #include "siren_chain.h"
 
 namespace mri {
@@ -39,7 +40,6 @@ namespace {
 using namespace chain;
 
 constexpr int kGradMaxIn = 4;   // axes the eight-slot form holds (the four-slot form: 3)
-constexpr int kGradMaxBlocks = 256;
 
 // Geometry for hidden width H: that of the forward kernel (image rows of a tile: 64, 128, 256, 256 for H = 256 .. 32),
 // the rows counted in points of SL image rows: 4 (value, d/dx_0, d/dx_1, d/dx_2) for dim_in <= 3, 8 (value, d/dx_0 ..
@@ -211,9 +211,18 @@ __global__ __launch_bounds__(kThreads) void siren_gradient_kernel(const GradArgs
 }
 
 // dim_in = 4 is served by the eight-slot form for exactly the cases of the four-slot form.
+int check_gradient_shape(const char* what, int dim_in, int hidden, int n_sine, int dim_out) {
+  MRI_REQUIRE(hidden == 32 || hidden == 64 || hidden == 128 || hidden == 256,
+              "%s: hidden = %d is not supported (32 / 64 / 128 / 256)", what, hidden);
+  MRI_REQUIRE(dim_in >= 1 && dim_in <= kGradMaxIn, "%s: dim_in = %d is not supported (1 .. %d)", what, dim_in,
+              kGradMaxIn);
+  MRI_REQUIRE(n_sine >= 1 && n_sine <= kMaxSine, "%s: n_sine_layers = %d is not supported (1 .. %d)", what, n_sine,
+              kMaxSine);
+  MRI_REQUIRE(dim_out == 1, "%s: dim_out = %d is not supported (1)", what, dim_out);
+  return MRI_OK;
+}
 bool gradient_supported(int dim_in, int hidden, int n_sine, int dim_out) {
-  return (hidden == 32 || hidden == 64 || hidden == 128 || hidden == 256) && dim_in >= 1 &&
-         dim_in <= kGradMaxIn && n_sine >= 1 && n_sine <= kMaxSine && dim_out == 1;
+  return check_gradient_shape("SIREN gradient", dim_in, hidden, n_sine, dim_out) == MRI_OK;
 }
 
 int64_t gradient_split_bytes(int hidden, int n_sine) {
@@ -223,8 +232,7 @@ int64_t gradient_split_bytes(int hidden, int n_sine) {
 template <int H, int SL>
 int launch_slots(const GradArgs& a, hipStream_t st) {
   using S = GradShape<H, SL>;
-  const int blocks = (int)std::min<int64_t>(ceil_div(a.n, S::points), kGradMaxBlocks);  // one workgroup per CU
-  hipLaunchKernelGGL((siren_gradient_kernel<S>), dim3(blocks), dim3(kThreads), 0, st, a);
+  hipLaunchKernelGGL((siren_gradient_kernel<S>), dim3(persistent_blocks(a.n, S::points)), dim3(kThreads), 0, st, a);
   return check_launch("siren_gradient_kernel");
 }
 
@@ -252,29 +260,20 @@ extern "C" int mri_siren_gradient(const float* x, int64_t n, int32_t dim_in, int
                                   int32_t n_sine_layers, const float* const* weight,
                                   const float* const* bias, float w0_first, float w0, float* y, float* dydx,
                                   void* workspace, int64_t workspace_bytes, void* stream) {
-  MRI_REQUIRE(hidden == 32 || hidden == 64 || hidden == 128 || hidden == 256,
-              "SIREN gradient: hidden = %d is not supported (32 / 64 / 128 / 256)", hidden);
-  MRI_REQUIRE(dim_in >= 1 && dim_in <= kGradMaxIn, "SIREN gradient: dim_in = %d is not supported (1 .. %d)", dim_in,
-              kGradMaxIn);
-  MRI_REQUIRE(n_sine_layers >= 1 && n_sine_layers <= kMaxSine,
-              "SIREN gradient: n_sine_layers = %d is not supported (1 .. %d)", n_sine_layers, kMaxSine);
-  if (int rc = check_gradient_io(x, n, y, dydx)) return rc;
+  const char* const what = "SIREN gradient";
+  MRI_CHECK(check_gradient_shape(what, dim_in, hidden, n_sine_layers, 1));
+  MRI_CHECK(check_gradient_io(x, n, y, dydx));
   if (n == 0) return MRI_OK;
-  MRI_REQUIRE(weight, "weight is NULL");
-  MRI_REQUIRE(bias, "bias is NULL");
-  const int64_t need = gradient_split_bytes(hidden, n_sine_layers);
-  MRI_REQUIRE(need == 0 || (workspace && workspace_bytes >= need && aligned_to(workspace, 16)),
-              "workspace: the SIREN gradient needs %lld bytes, 16-byte aligned (mri_siren_gradient_workspace_bytes)",
-              (long long)need);
+  MRI_CHECK(check_buffers({{"weight", weight}, {"bias", bias}}, kAnyAlignment));
+  MRI_CHECK(check_workspace(what, "mri_siren_gradient_workspace_bytes", workspace, workspace_bytes,
+                            gradient_split_bytes(hidden, n_sine_layers)));
+  MRI_CHECK(check_pointers({{"weight", weight}}, 0, n_sine_layers + 1, 16));
+  MRI_CHECK(check_pointers({{"bias", bias}}, 0, n_sine_layers + 1, kAnyAlignment));
   GradArgs a{};
   a.x = x, a.n = n, a.dim_in = dim_in, a.n_sine = n_sine_layers;
   a.w0_first = w0_first, a.w0 = w0, a.y = y, a.dydx = dydx;
-  for (int l = 0; l <= n_sine_layers; ++l) {
-    MRI_REQUIRE(weight[l], "weight[%d] is NULL", l);
-    MRI_REQUIRE(bias[l], "bias[%d] is NULL", l);
-    MRI_REQUIRE(aligned_to(weight[l], 16), "weight[%d] must be 16-byte aligned", l);
-    a.w[l] = weight[l], a.b[l] = bias[l];
-  }
+  std::copy(weight, weight + n_sine_layers + 1, a.w);
+  std::copy(bias, bias + n_sine_layers + 1, a.b);
   a.wsplit = static_cast<const char*>(workspace);
   hipStream_t st = (hipStream_t)stream;
   if (int rc = split_weights_ld(weight + 1, n_sine_layers - 1, hidden, hidden, false, static_cast<char*>(workspace),

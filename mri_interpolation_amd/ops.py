@@ -99,6 +99,71 @@ def hashgrid_forward(desc: GridDesc, x: torch.Tensor, table: torch.Tensor,
     return out
 
 
+def _grow_scratch(cache, device, need_bytes, dtype=torch.float32):
+    """The process-wide scratch of one kernel family: one tensor per device in the dict `cache` (device index ->
+    tensor), of at least need_bytes.  It only ever grows; before a larger one replaces it the device is synchronised,
+    so no kernel of any stream can still be using the buffer that goes back to the allocator.  need_bytes <= 0 (a call
+    that needs none, or a shape the library is about to refuse with its reason): whatever is cached, else 64 elements
+    (floats, by default) that are not kept."""
+    ws = cache.get(device.index)
+    if need_bytes <= 0:
+        return ws if ws is not None else torch.empty(64, dtype=dtype, device=device)
+    if ws is None or ws.numel() * ws.element_size() < need_bytes:
+        if ws is not None:
+            torch.cuda.synchronize(device)
+        size = torch.empty((), dtype=dtype).element_size()
+        ws = cache[device.index] = torch.empty((need_bytes + size - 1) // size, dtype=dtype, device=device)
+    return ws
+
+
+def _outputs(what, x, y, dydx=False):
+    """y (n, 1) of a chain call on x (n, dim_in) and, unless dydx is False, dydx (n, dim_in): allocated where None,
+    else held to their sizes (the library sees pointers only)."""
+    n, dim_in = x.shape[0], x.shape[-1]
+    if y is None:
+        y = torch.empty((n, 1), device=x.device, dtype=torch.float32)
+    if y.numel() != n:
+        raise ValueError(f"{what}: y holds n values")
+    if dydx is False:
+        return y
+    if dydx is None:
+        dydx = torch.empty((n, dim_in), device=x.device, dtype=torch.float32)
+    if dydx.shape != (n, dim_in):
+        raise ValueError(f"{what}: y holds n values, dydx is (n, dim_in)")
+    return y, dydx
+
+
+def _check_stack(what, weights, want, vectors=(), matrices=(), label="Linear", at_least=2, buffers=None, flat=None,
+                 extra=()):
+    """What the library cannot see behind its pointers (a mismatched shape would be read or written out of bounds on
+    the device).  A stack of Linears: weights[i] is of shape want[i] (want None: not held to shapes), every list of
+    `vectors` holds one (want[i][0],) tensor per weight (biases, their gradients), every list of `matrices` one of shape
+    want[i] (weight gradients).  buffers = (n, hidden, count, {name: list}): `count` per-layer (n, hidden) tensors in
+    each list (an entry may be None where the library takes NULL); flat = (n, {name: tensor}): n values each; `extra`:
+    further tensors.  Everything contiguous float32."""
+    per_weight = list(vectors) + list(matrices)
+    if len(weights) < at_least or any(len(o) != len(weights) for o in per_weight):
+        raise ValueError(f"{what}: at least {at_least} {label}s, one bias / gradient per weight")
+    for i, shape in enumerate(want or ()):
+        got = [tuple(o[i].shape) for o in [weights] + list(matrices)], [tuple(v[i].shape) for v in vectors]
+        if any(s != shape for s in got[0]) or any(s != (shape[0],) for s in got[1]):
+            raise ValueError(f"{what}: {label} {i} is {shape} with a bias of {shape[0]}, got {got[0]} and {got[1]}")
+    n, hidden, count, lists = buffers or (0, 0, 0, {})
+    for name, seq in lists.items():
+        if len(seq) != count:
+            raise ValueError(f"{what}: {name} needs {count} (n, hidden) buffers, one per layer")
+        if any(t is not None and tuple(t.shape) != (n, hidden) for t in seq):
+            raise ValueError(f"{what}: {name} buffers are (n, hidden) = ({n}, {hidden})")
+    n, named = flat or (0, {})
+    for name, t in named.items():
+        if t.numel() != n:
+            raise ValueError(f"{what}: {name} holds n = {n} values")
+    every = list(weights) + [t for o in per_weight for t in o] + [t for s in lists.values() for t in s if t is not None]
+    for t in every + list(named.values()) + list(extra):
+        if not t.is_contiguous() or t.dtype != torch.float32:
+            raise ValueError(f"{what} needs contiguous float32 parameters and buffers")
+
+
 _bwd_workspace = {}  # device index -> scratch (the library clears what it needs per call)
 
 
@@ -110,17 +175,8 @@ def backward_workspace_bytes(desc: GridDesc, n: int) -> int:
 
 
 def backward_workspace(desc: GridDesc, n: int, device) -> torch.Tensor:
-    """Process-wide scratch of the module / autograd path (FusedStep owns its own buffer).  It
-    only ever grows; before a larger one replaces it the device is synchronised, so no kernel of
-    any stream can still be using the buffer that goes back to the allocator."""
-    need = backward_workspace_bytes(desc, n)
-    ws = _bwd_workspace.get(device.index)
-    if ws is None or ws.numel() * 8 < need:
-        if ws is not None:
-            torch.cuda.synchronize(device)
-        ws = torch.empty((need + 7) // 8, dtype=torch.int64, device=device)
-        _bwd_workspace[device.index] = ws
-    return ws
+    """Process-wide scratch of the module / autograd path (FusedStep owns its own buffer): _grow_scratch."""
+    return _grow_scratch(_bwd_workspace, device, backward_workspace_bytes(desc, n), torch.int64)
 
 
 def hashgrid_backward_prepare(desc: GridDesc, x: torch.Tensor, method: int = 0, stream=None,
@@ -485,37 +541,18 @@ def rff_forward_supported(dim_in: int, hidden: int, n_frequencies: int, n_layers
 _rff_ws = {}
 
 
-def _rff_check(what, x, b, weights, biases, outputs):
-    """(n, dim_in, hidden, n_layers) of an inference call.  The library sees pointers only: a mismatched shape would be
-    read out of bounds on the device."""
+def _rff_check(what, x, b, weights, vectors=(), matrices=(), per_layer=None, flat=None, extra=()):
+    """(n, dim_in, hidden, n_layers) of an RffNet call, held to _check_stack: b (n_frequencies, dim_in), the first
+    Linear on the 2 n_frequencies encoded features, one (n, hidden) buffer per hidden Linear in each list of
+    `per_layer`, n values in each tensor of `flat`."""
     n, dim_in = x.shape
     n_layers, hidden = len(weights), weights[0].shape[0]
-    if len(biases) != n_layers or n_layers < 2:
-        raise ValueError(f"{what}: at least two Linears, one bias per weight")
     if b.dim() != 2 or b.shape[1] != dim_in:
         raise ValueError(f"{what}: b is (n_frequencies, dim_in = {dim_in}), got {tuple(b.shape)}")
     want = [(hidden, 2 * b.shape[0])] + [(hidden, hidden)] * (n_layers - 2) + [(1, hidden)]
-    for i, (w, v, shape) in enumerate(zip(weights, biases, want)):
-        if tuple(w.shape) != shape or tuple(v.shape) != (shape[0],):
-            raise ValueError(f"{what}: Linear {i} is {shape} with a bias of {shape[0]}, got {tuple(w.shape)} and "
-                             f"{tuple(v.shape)}")
-    for t in [b] + list(outputs) + list(weights) + list(biases):
-        if not t.is_contiguous() or t.dtype != torch.float32:
-            raise ValueError(f"{what} needs contiguous float32 parameters and buffers")
+    _check_stack(what, weights, want, vectors, matrices, buffers=(n, hidden, n_layers - 1, per_layer or {}),
+                 flat=(n, flat or {}), extra=[b] + list(extra))
     return n, dim_in, hidden, n_layers
-
-
-def _rff_scratch(device, need):
-    """The inference calls' workspace (the split weights), one per device, grown on demand."""
-    ws = _rff_ws.get(device.index)
-    if need > 0 and (ws is None or ws.numel() * 4 < need):
-        if ws is not None:
-            torch.cuda.synchronize(device)
-        ws = torch.empty((need + 3) // 4, dtype=torch.float32, device=device)
-        _rff_ws[device.index] = ws
-    if ws is None:  # (the library refuses the shape with its reason)
-        ws = torch.empty(64, dtype=torch.float32, device=device)
-    return ws
 
 
 def rff_forward(x, b, weights, biases, y=None):
@@ -523,12 +560,9 @@ def rff_forward(x, b, weights, biases, y=None):
     two LDS images, nothing (n, hidden)-sized is written.  weights / biases: the decoder's Linears, the head last."""
     _gpu(x, b, y, *weights, *biases)
     x = _rowmajor(x).contiguous()
-    if y is None:
-        y = torch.empty((x.shape[0], 1), device=x.device, dtype=torch.float32)
-    if y.numel() != x.shape[0]:
-        raise ValueError("rff_forward: y holds n values")
-    n, dim_in, hidden, n_layers = _rff_check("rff_forward", x, b, weights, biases, [y])
-    ws = _rff_scratch(x.device, _lib.load().mri_rff_forward_workspace_bytes(hidden, n_layers))
+    y = _outputs("rff_forward", x, y)
+    n, dim_in, hidden, n_layers = _rff_check("rff_forward", x, b, weights, [biases], extra=[y])
+    ws = _grow_scratch(_rff_ws, x.device, _lib.load().mri_rff_forward_workspace_bytes(hidden, n_layers))
     _lib.call("mri_rff_forward", _ptr(x), n, dim_in, hidden, b.shape[0], n_layers, _ptr(b), _ptr_array(weights),
               _ptr_array(biases), _ptr(y), _ptr(ws), ws.numel() * 4, _stream())
     return y
@@ -545,14 +579,9 @@ def rff_gradient(x, b, weights, biases, y=None, dydx=None):
     rff_forward's bit for bit.  Parameters as rff_forward."""
     _gpu(x, b, y, dydx, *weights, *biases)
     x = _rowmajor(x).contiguous()
-    if y is None:
-        y = torch.empty((x.shape[0], 1), device=x.device, dtype=torch.float32)
-    if dydx is None:
-        dydx = torch.empty(tuple(x.shape), device=x.device, dtype=torch.float32)
-    if y.numel() != x.shape[0] or dydx.shape != x.shape:
-        raise ValueError("rff_gradient: y holds n values, dydx is (n, dim_in)")
-    n, dim_in, hidden, n_layers = _rff_check("rff_gradient", x, b, weights, biases, [y, dydx])
-    ws = _rff_scratch(x.device, _lib.load().mri_rff_gradient_workspace_bytes(hidden, n_layers))
+    y, dydx = _outputs("rff_gradient", x, y, dydx)
+    n, dim_in, hidden, n_layers = _rff_check("rff_gradient", x, b, weights, [biases], extra=[y, dydx])
+    ws = _grow_scratch(_rff_ws, x.device, _lib.load().mri_rff_gradient_workspace_bytes(hidden, n_layers))
     _lib.call("mri_rff_gradient", _ptr(x), n, dim_in, hidden, b.shape[0], n_layers, _ptr(b), _ptr_array(weights),
               _ptr_array(biases), _ptr(y), _ptr(dydx), _ptr(ws), ws.numel() * 4, _stream())
     return y, dydx
@@ -577,48 +606,9 @@ def _rff_train_scratch(device, n, hidden, n_layers, ws):
     if ws is not None:  # the caller's own (FusedStep's, one per batch size): the library checks its size
         _gpu(ws)
         return ws
-    need = _lib.load().mri_rff_backward_workspace_bytes(max(int(n), 1), hidden, n_layers)
-    if need < 0:  # (the library refuses the shape with its reason)
-        return torch.empty(64, dtype=torch.float32, device=device)
-    ws = _rff_train_ws.get(device.index)
-    if ws is None or ws.numel() * 4 < need:
-        if ws is not None:
-            torch.cuda.synchronize(device)
-        ws = torch.empty((need + 3) // 4, dtype=torch.float32, device=device)
-        _rff_train_ws[device.index] = ws
-    return ws
-
-
-def _rff_train_check(what, x, b, weights, others, per_layer, flat):
-    """What the library cannot see behind its pointers: the shapes of b and the Linears, one (n, hidden) buffer per
-    hidden Linear in each of `per_layer`, n values in each of `flat`; everything contiguous float32."""
-    n, dim_in = x.shape
-    n_layers, hidden = len(weights), weights[0].shape[0]
-    if n_layers < 2 or any(len(o) != n_layers for o in others):
-        raise ValueError(f"{what}: at least two Linears, one bias / gradient per weight")
-    if b.dim() != 2 or b.shape[1] != dim_in:
-        raise ValueError(f"{what}: b is (n_frequencies, dim_in = {dim_in}), got {tuple(b.shape)}")
-    want = [(hidden, 2 * b.shape[0])] + [(hidden, hidden)] * (n_layers - 2) + [(1, hidden)]
-    for i, shape in enumerate(want):
-        if tuple(weights[i].shape) != shape:
-            raise ValueError(f"{what}: Linear {i} is {shape}, got {tuple(weights[i].shape)}")
-        for o in others:
-            if tuple(o[i].shape) not in (shape, (shape[0],)):
-                raise ValueError(f"{what}: Linear {i} takes {shape} / ({shape[0]},) tensors, got {tuple(o[i].shape)}")
-    for name, seq in per_layer.items():
-        if len(seq) != n_layers - 1:
-            raise ValueError(f"{what}: {name} needs one (n, hidden) buffer per hidden Linear")
-        if any(tuple(t.shape) != (n, hidden) for t in seq):
-            raise ValueError(f"{what}: {name} buffers are (n, hidden)")
-    for name, t in flat.items():
-        if t.numel() != n:
-            raise ValueError(f"{what}: {name} holds n values")
-    every = [b] + list(weights) + [t for o in others for t in o] + [t for s in per_layer.values() for t in s] \
-        + list(flat.values())
-    for t in every:
-        if not t.is_contiguous() or t.dtype != torch.float32:
-            raise ValueError(f"{what} needs contiguous float32 parameters and buffers")
-    return n, dim_in, hidden, n_layers
+    # (need < 0: the library refuses the shape with its reason)
+    return _grow_scratch(_rff_train_ws, device,
+                         _lib.load().mri_rff_backward_workspace_bytes(max(int(n), 1), hidden, n_layers))
 
 
 def rff_forward_loss(x, target, b, weights, biases, act, y, dy, loss_out, n_total=None, grad_divisor: float = 1.0,
@@ -629,8 +619,8 @@ def rff_forward_loss(x, target, b, weights, biases, act, y, dy, loss_out, n_tota
     _gpu(x, target, b, y, dy, loss_out, ws, *weights, *biases, *act)
     x = _rowmajor(x).contiguous()
     target = target.reshape(-1).contiguous()
-    n, dim_in, hidden, n_layers = _rff_train_check("rff_forward_loss", x, b, weights, [biases], dict(act=act),
-                                                   dict(target=target, y=y, dy=dy))
+    n, dim_in, hidden, n_layers = _rff_check("rff_forward_loss", x, b, weights, [biases], per_layer=dict(act=act),
+                                             flat=dict(target=target, y=y, dy=dy))
     if target.dtype != torch.float32 or loss_out.dtype != torch.float32 or loss_out.numel() < 1:
         raise ValueError("rff_forward_loss needs a float32 target and a float32 loss_out of one element")
     ws = _rff_train_scratch(x.device, n, hidden, n_layers, ws)
@@ -646,8 +636,8 @@ def rff_backward(x, dy, b, weights, act, dz, d_weights, d_biases, ws=None):
     Gradients are ADDED to d_weights / d_biases (one per Linear, the head last).  b gets none: it is frozen."""
     _gpu(x, dy, b, ws, *weights, *act, *dz, *d_weights, *d_biases)
     x = _rowmajor(x).contiguous()
-    n, dim_in, hidden, n_layers = _rff_train_check("rff_backward", x, b, weights, [d_weights, d_biases],
-                                                   dict(act=act, dz=dz), dict(dy=dy))
+    n, dim_in, hidden, n_layers = _rff_check("rff_backward", x, b, weights, [d_biases], [d_weights],
+                                             per_layer=dict(act=act, dz=dz), flat=dict(dy=dy))
     ws = _rff_train_scratch(x.device, n, hidden, n_layers, ws)
     _lib.call("mri_rff_backward", _ptr(x), _ptr(dy), n, dim_in, hidden, b.shape[0], n_layers, _ptr(b),
               _ptr_array(weights), _ptr_array(act), _ptr_array(dz), _ptr_array(d_weights), _ptr_array(d_biases),
@@ -720,32 +710,13 @@ def _gabor_check(what, x, freq_weights, freq_biases, scale_weights, scale_biases
         raise ValueError(f"{what}: x is float32 (n, dim_in), got {x.dtype} {tuple(x.shape)}")
     n, dim_in = x.shape
     n_layers = len(freq_weights)
-    if n_layers < 2 or any(len(t) != n_layers for t in (freq_biases, scale_weights, scale_biases)):
-        raise ValueError(f"{what}: at least two layers, a freqs and a scale Linear with a bias each per layer")
-    hidden = freq_weights[0].shape[0]
+    if len(scale_weights) != n_layers:
+        raise ValueError(f"{what}: a freqs and a scale Linear per layer")
+    hidden = freq_weights[0].shape[0] if n_layers else 0
     want = [(hidden, dim_in)] + [(hidden, hidden)] * (n_layers - 2) + [(1, hidden)]
-    for name, ws, bs in (("freqs", freq_weights, freq_biases), ("scale", scale_weights, scale_biases)):
-        for i, (w, v, shape) in enumerate(zip(ws, bs, want)):
-            if tuple(w.shape) != shape or tuple(v.shape) != (shape[0],):
-                raise ValueError(f"{what}: {name} of layer {i} is {shape} with a bias of {shape[0]}, got "
-                                 f"{tuple(w.shape)} and {tuple(v.shape)}")
-    for t in list(outputs) + list(freq_weights) + list(freq_biases) + list(scale_weights) + list(scale_biases):
-        if not t.is_contiguous() or t.dtype != torch.float32:
-            raise ValueError(f"{what} needs contiguous float32 parameters and buffers")
+    _check_stack(what, freq_weights, want, [freq_biases], label="freqs Linear", extra=outputs)
+    _check_stack(what, scale_weights, want, [scale_biases], label="scale Linear")
     return n, dim_in, hidden, n_layers
-
-
-def _gabor_scratch(device, need):
-    """The inference call's workspace (the split weights), one per device, grown on demand."""
-    ws = _gabor_ws.get(device.index)
-    if need > 0 and (ws is None or ws.numel() * 4 < need):
-        if ws is not None:
-            torch.cuda.synchronize(device)
-        ws = torch.empty((need + 3) // 4, dtype=torch.float32, device=device)
-        _gabor_ws[device.index] = ws
-    if ws is None:  # (two layers need none; an unsupported shape is refused by the library with its reason)
-        ws = torch.empty(64, dtype=torch.float32, device=device)
-    return ws
 
 
 def gabor_forward(x, freq_weights, freq_biases, scale_weights, scale_biases, w0: float, c: float, y=None):
@@ -753,13 +724,10 @@ def gabor_forward(x, freq_weights, freq_biases, scale_weights, scale_biases, w0:
     the head included; nothing (n, hidden)-sized is written.  The four lists hold the layers' parameters, the head last."""
     _gpu(x, y, *freq_weights, *freq_biases, *scale_weights, *scale_biases)
     x = _rowmajor(x).contiguous()
-    if y is None:
-        y = torch.empty((x.shape[0], 1), device=x.device, dtype=torch.float32)
-    if y.numel() != x.shape[0]:
-        raise ValueError("gabor_forward: y holds n values")
+    y = _outputs("gabor_forward", x, y)
     n, dim_in, hidden, n_layers = _gabor_check("gabor_forward", x, freq_weights, freq_biases, scale_weights,
                                                scale_biases, [y])
-    ws = _gabor_scratch(x.device, _lib.load().mri_gabor_forward_workspace_bytes(hidden, n_layers))
+    ws = _grow_scratch(_gabor_ws, x.device, _lib.load().mri_gabor_forward_workspace_bytes(hidden, n_layers))
     _lib.call("mri_gabor_forward", _ptr(x), n, dim_in, hidden, n_layers, _ptr_array(freq_weights),
               _ptr_array(freq_biases), _ptr_array(scale_weights), _ptr_array(scale_biases), float(w0), float(c), _ptr(y),
               _ptr(ws), ws.numel() * 4, _stream())
@@ -775,14 +743,7 @@ _mlp_workspace = {}
 
 
 def _tiny_workspace(k_in, hidden, n, device):
-    need = _lib.load().mri_tiny_mlp_workspace_bytes(k_in, hidden, n)
-    ws = _mlp_workspace.get(device.index)
-    if ws is None or ws.numel() * 4 < need:
-        if ws is not None:  # may still be in use on another stream: see backward_workspace()
-            torch.cuda.synchronize(device)
-        ws = torch.empty((need + 3) // 4, dtype=torch.float32, device=device)
-        _mlp_workspace[device.index] = ws
-    return ws
+    return _grow_scratch(_mlp_workspace, device, _lib.load().mri_tiny_mlp_workspace_bytes(k_in, hidden, n))
 
 
 def tiny_mlp_forward(x_fm, params, y=None):
@@ -894,13 +855,7 @@ def _shallow_workspace(k_in, hidden, n, device):
     need = _lib.load().mri_shallow_mlp_workspace_bytes(k_in, hidden, n)
     if need < 0:
         raise ValueError(f"shallow decoder {k_in} -> {hidden} -> 1 is not supported")
-    ws = _shallow_workspace_cache.get(device.index)
-    if ws is None or ws.numel() * 4 < need:
-        if ws is not None:  # may still be in use on another stream: see backward_workspace()
-            torch.cuda.synchronize(device)
-        ws = torch.empty((need + 3) // 4, dtype=torch.float32, device=device)
-        _shallow_workspace_cache[device.index] = ws
-    return ws
+    return _grow_scratch(_shallow_workspace_cache, device, need)
 
 
 def shallow_mlp_forward(x_fm, params, activations, y=None):
@@ -1022,14 +977,7 @@ _siren_workspace = {}
 
 
 def _siren_scratch(device, n, hidden, n_sine):
-    need = _lib.load().mri_siren_backward_workspace_bytes(n, hidden, n_sine)
-    ws = _siren_workspace.get(device.index)
-    if ws is None or ws.numel() * 4 < need:
-        if ws is not None:
-            torch.cuda.synchronize(device)
-        ws = torch.empty((need + 3) // 4, dtype=torch.float32, device=device)
-        _siren_workspace[device.index] = ws
-    return ws
+    return _grow_scratch(_siren_workspace, device, _lib.load().mri_siren_backward_workspace_bytes(n, hidden, n_sine))
 
 
 def siren_gradient_supported(dim_in: int, hidden: int, n_sine_layers: int, dim_out: int) -> bool:
@@ -1045,12 +993,7 @@ def siren_gradient(x, weights, biases, w0_first: float, w0: float, y=None, dydx=
     x = _rowmajor(x).contiguous()
     n, dim_in = x.shape
     n_sine, hidden = len(weights) - 1, weights[0].shape[0]
-    if y is None:
-        y = torch.empty((n, 1), device=x.device, dtype=torch.float32)
-    if dydx is None:
-        dydx = torch.empty((n, dim_in), device=x.device, dtype=torch.float32)
-    if y.numel() != n or dydx.shape != (n, dim_in):
-        raise ValueError("siren_gradient: y holds n values, dydx is (n, dim_in)")
+    y, dydx = _outputs("siren_gradient", x, y, dydx)
     for t in list(weights) + list(biases) + [y, dydx]:
         if not t.is_contiguous():
             raise ValueError("siren_gradient needs contiguous parameters and buffers")
@@ -1138,27 +1081,12 @@ def _modsiren_scratch(device, n, hidden, n_layers, ws, need=None):
         return ws
     if need is None:  # (the gradient call passes its own: the split weights alone, whatever n)
         need = _lib.load().mri_modsiren_backward_workspace_bytes(max(int(n), 1), hidden, n_layers)
-    if need < 0:  # (the library refuses the shape with its reason)
-        return torch.empty(64, dtype=torch.float32, device=device)
-    ws = _modsiren_ws.get(device.index)
-    if ws is None or ws.numel() * 4 < need:
-        if ws is not None:
-            torch.cuda.synchronize(device)
-        ws = torch.empty((need + 3) // 4, dtype=torch.float32, device=device)
-        _modsiren_ws[device.index] = ws
-    return ws
+    return _grow_scratch(_modsiren_ws, device, need)  # (need < 0: the library refuses the shape with its reason)
 
 
 def _modsiren_check(what, n, hidden, n_layers, per_layer, params):
-    for name, seq in per_layer.items():
-        if len(seq) != n_layers:
-            raise ValueError(f"{what}: {name} needs one (n, hidden) buffer per layer")
-        for t in seq:
-            if t is not None and (tuple(t.shape) != (n, hidden) or not t.is_contiguous() or t.dtype != torch.float32):
-                raise ValueError(f"{what}: {name} buffers are contiguous float32 (n, hidden)")
-    for t in params:
-        if not t.is_contiguous() or t.dtype != torch.float32:
-            raise ValueError(f"{what} needs contiguous float32 parameters and buffers")
+    """_check_stack of the per-layer (n, hidden) buffers and the parameters, the latter not held to shapes."""
+    _check_stack(what, params, None, at_least=0, buffers=(n, hidden, n_layers, per_layer))
 
 
 def modsiren_forward(x, siren_weights, siren_biases, mod_weights, mod_biases, w0_first: float, w0: float,
@@ -1203,12 +1131,7 @@ def modsiren_gradient(x, siren_weights, siren_biases, mod_weights, mod_biases, w
     n_layers, hidden = len(mod_weights), mod_weights[0].shape[0]
     if len(siren_weights) != n_layers + 1 or len(siren_biases) != n_layers + 1 or len(mod_biases) != n_layers:
         raise ValueError("modsiren_gradient: n_layers + 1 SIREN weights / biases (the head last), n_layers modulator's")
-    if y is None:
-        y = torch.empty((n, 1), device=x.device, dtype=torch.float32)
-    if dydx is None:
-        dydx = torch.empty((n, dim_in), device=x.device, dtype=torch.float32)
-    if y.numel() != n or dydx.shape != (n, dim_in):
-        raise ValueError("modsiren_gradient: y holds n values, dydx is (n, dim_in)")
+    y, dydx = _outputs("modsiren_gradient", x, y, dydx)
     _modsiren_check("modsiren_gradient", n, hidden, n_layers, {},
                     list(siren_weights) + list(siren_biases) + list(mod_weights) + list(mod_biases) + [y, dydx])
     ws = _modsiren_scratch(x.device, n, hidden, n_layers, None,  # holds the split weights

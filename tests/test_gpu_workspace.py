@@ -55,8 +55,9 @@ Inventory: every entry point that takes a workspace | its size function | cases
   mri_fused_step                 | tiny_ws, bwd_ws, next_bwd_ws | test_fused_step: two consecutive steps, the
                                    counted-ahead workspace of step 1 is the bwd_ws of step 2
 The Python owners of scratch -- ops.backward_workspace, _tiny_workspace, _shallow_workspace, _siren_scratch,
-modsiren_workspace (test_ops_*) and trainer.FusedStep, one case per plan (test_fused_step_owns_clean_scratch) -- are
-grown by a large call of another shape, filled with 0xFF bytes and held to the bits of the zero-filled run.
+modsiren_workspace, the caches _rff_ws, _rff_train_ws, _gabor_ws and _modsiren_ws (test_ops_*) and trainer.FusedStep,
+one case per plan (test_fused_step_owns_clean_scratch) -- are grown by a large call of another shape, filled with 0xFF
+bytes and held to the bits of the zero-filled run.  (The pool they all call, ops._grow_scratch: test_scratch_cpu.py.)
 """
 import ctypes as C
 import functools
@@ -1176,6 +1177,89 @@ def test_ops_modsiren_workspace(amd):
     for name, value in got.items():
         assert torch.equal(bits(value), bits(base[name])), f"ops.modsiren_workspace: {name} differs on 0xFF bytes"
     judge_modsiren(modsiren_refs(hidden, L, n, dim_in), "ops.modsiren_*")({k: v.cpu() for k, v in base.items()})
+
+
+def test_ops_rff_scratch(amd):
+    """ops._rff_ws behind rff_forward and rff_gradient: the references and the judgement of test_gpu_rff_gradient.py."""
+    from test_gpu_rff_gradient import reference
+    from test_gpu_rff_step import close_or_no_worse as judge, he_init, selected_rows, uniform as unit
+    ops = amd.ops
+    x_all, _, b, params, r64, r32 = selected_rows(2, 64, 3)
+    x = x_all[:300].contiguous()
+
+    def run(x, b, params):
+        bc, ws, bs = b.cuda(), [w.cuda() for w, _ in params], [v.cuda() for _, v in params]
+        n, d = x.shape
+        y, y2, dydx = (torch.full(s, NAN, device="cuda") for s in ((n, 1), (n, 1), (n, d)))
+        ops.rff_forward(x.cuda(), bc, ws, bs, y=y)
+        ops.rff_gradient(x.cuda(), bc, ws, bs, y=y2, dydx=dydx)
+        return dict(y=y.reshape(-1), gradient_y=y2.reshape(-1), dydx=dydx)
+    base = owner_runs(amd, ops._rff_ws, lambda: run(unit((300, 3), 41), *he_init(3, 128, 4, 9741, 1.0)),
+                      lambda: run(x, b, params), "ops._rff_ws")
+    (y32, g32, _), (y64, g64, _) = reference(r32, x), reference(r64, x)
+    for name, f32, f64 in (("y", y32, y64), ("gradient_y", y32, y64), ("dydx", g32, g64)):
+        judge(base[name].cpu().numpy(), f32.numpy(), f64.numpy(), f"ops.rff_forward / rff_gradient: {name}")
+
+
+def test_ops_rff_train_scratch(amd):
+    """ops._rff_train_ws behind rff_forward_loss + rff_backward without a workspace of the caller's: the references and
+    the judgement of test_gpu_rff_step.py."""
+    from test_gpu_rff_step import close_or_no_worse as judge, he_init, kernel_pass, names, scalar, selected_rows, \
+        uniform as unit
+    x_all, y_all, b, params, r64, r32 = selected_rows(2, 64, 3)
+    x, t = x_all[:300].contiguous(), y_all[:300].contiguous()
+
+    def run(x, t, b, params):
+        y, dy, loss, grads = kernel_pass(amd, b, params, x, t)
+        return dict(zip(names(len(params)), grads), y=y, dy=dy, loss=loss)
+    base = owner_runs(amd, amd.ops._rff_train_ws,
+                      lambda: run(unit((3001, 3), 42), unit((3001, 1), 43), *he_init(3, 128, 4, 9742, 1.0)),
+                      lambda: run(x, t, b, params), "ops._rff_train_ws")
+    (p32, l32, g32), (p64, l64, g64) = r32.loss_and_grads(x, t), r64.loss_and_grads(x, t)
+    judge(base["y"].cpu().numpy(), p32.numpy(), p64.numpy(), "ops.rff_forward_loss: y")
+    judge(scalar(base["loss"]), scalar(l32), scalar(l64), "ops.rff_forward_loss: loss")
+    for name, c32, c64 in zip(names(len(params)), g32, g64):
+        judge(base[name].cpu().numpy(), c32.numpy(), c64.numpy(), f"ops.rff_backward: {name}")
+
+
+def test_ops_gabor_scratch(amd):
+    """ops._gabor_ws behind gabor_forward: the reference and the judgement of test_gpu_gabor.py."""
+    import gabor_ref
+    from test_gpu_gabor import device_params, fused_case
+    w0, c = 5.0, 1.0
+    x, params, y32, y64 = fused_case(2, 64, 3, w0, c, 300)
+
+    def run(x, params):
+        y = torch.full((x.shape[0], 1), NAN, device="cuda")
+        amd.ops.gabor_forward(x.cuda(), *device_params(params), w0, c, y=y)
+        return dict(y=y.reshape(-1))
+    base = owner_runs(amd, amd.ops._gabor_ws,
+                      lambda: run(gabor_ref.uniform((300, 3), 44), gabor_ref.grid_params(3, 128, 4, 9744)),
+                      lambda: run(x, params), "ops._gabor_ws")
+    assert_no_worse(base["y"].cpu().numpy(), y32.numpy(), y64.numpy(), "ops.gabor_forward: y")
+
+
+def test_ops_modsiren_scratch(amd):
+    """ops._modsiren_ws behind the inference form of modsiren_forward and modsiren_gradient, neither with a workspace of
+    the caller's: modsiren_refs and, for dydx, float64 autograd through it (test_gpu_modsiren_gradient.reference)."""
+    from test_gpu_modsiren_gradient import reference
+    ops = amd.ops
+    small, big = (64, 2, 300, 3), (128, 3, 3001, 3)
+
+    def run(hidden, L, n, dim_in):
+        siren, mod, x, _ = modsiren_inputs(hidden, L, n, dim_in)
+        par = [[p[k].cuda() for p in stack] for stack in (siren, mod) for k in (0, 1)]
+        y, y2, dydx = (torch.full(s, NAN, device="cuda") for s in ((n, 1), (n, 1), (n, dim_in)))
+        ops.modsiren_forward(x.cuda(), *par, 30.0, 30.0, y=y)
+        ops.modsiren_gradient(x.cuda(), *par, 30.0, 30.0, y=y2, dydx=dydx)
+        return dict(y=y.reshape(-1), gradient_y=y2.reshape(-1), dydx=dydx)
+    base = {k: v.cpu() for k, v in owner_runs(amd, ops._modsiren_ws, lambda: run(*big), lambda: run(*small),
+                                              "ops._modsiren_ws").items()}
+    judge_modsiren(modsiren_refs(*small), "ops.modsiren_forward")(dict(y=base["y"]))
+    judge_modsiren(modsiren_refs(*small), "ops.modsiren_gradient")(dict(y=base["gradient_y"]))
+    siren, mod, x, _ = modsiren_inputs(*small)
+    (_, g32), (_, g64) = (reference(x, siren, mod, 30.0, 30.0, dtype) for dtype in (torch.float32, torch.float64))
+    close_or_no_worse(base["dydx"].numpy(), g32.numpy(), g64.numpy(), "ops.modsiren_gradient: dydx")
 
 
 def _hash_net(models, **kw):
